@@ -16,6 +16,11 @@ seq, summed over ranks, divided by the max-over-ranks wall time).
 Timing bracket: torch.cuda.synchronize() + a gloo control-plane barrier on
 both sides of EXACTLY K steps (the gloo group keeps the bracket off the
 RCCL communicator that the com thread is using concurrently).
+
+A plain run does only that: set up, warm up, time the K steps, print the
+result line. --dump-outputs DIR additionally saves what the last timed step
+left behind (see dump_outputs); --full is reserved for secondary
+measurements that need runs of their own.
 """
 
 from __future__ import annotations
@@ -67,7 +72,36 @@ def parse_args():
     p.add_argument("--lr", type=float, default=6e-4)
     p.add_argument("--ckpt", action="store_true",
                    help="per-layer activation recompute (8B batch headroom)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, save the last step's loss, "
+                        "parameters and (acco/dpu) accumulated gradients as "
+                        "DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements that are not "
+                        "part of the headline figure (none at present: the "
+                        "plain run is the whole benchmark)")
     return p.parse_args()
+
+
+# elements kept per dumped array: 3 arrays x 2^21 x 4 B = 24 MiB at most
+DUMP_SAMPLE = 1 << 21
+
+
+def dump_outputs(out_dir, arrays):
+    """Save each tensor as out_dir/<name>.npy in float32. An array longer
+    than DUMP_SAMPLE is reduced to a fixed sample: the same seeded, sorted
+    indices for every run and every build, so two dumps compare element for
+    element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(2024)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g)
+            t = t[idx.sort().values.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.float().cpu().numpy())
 
 
 def make_batch_pool(n_pool, batch, seq, vocab, device, seed):
@@ -204,16 +238,22 @@ def main():
             eng.train_dpu(nb_grad_tot=1 << 60, n_warmup_steps=0,
                           max_rounds=warmup + steps)
         micro = state["mb1"] - state["mb0"]
+        # the last buffer update left the accumulated gradients in the com
+        # buffer (the grad arena itself is zeroed after even rounds)
+        outputs = {"loss": eng.loss_static, "params": eng.params[:n_live],
+                   "grads": eng.com_buffer[:n_live]}
     else:
         ddp = NativeZeroDDP(model, params, grads, n_live, spec, comm, rank, opt)
         micro_count = 0
+        last_loss = None
 
         def ddp_step():
-            nonlocal micro_count
+            nonlocal micro_count, last_loss
             ddp.begin_sync_microbatch()
             ids = next_batch()["input_ids"]
             loss, _ = model(ids, labels=ids)
             loss.backward()
+            last_loss = loss.detach()
             micro_count += 1
             ddp.finish_step(grad_scale=1.0 / world, lr=sched.lr())
             ddp.zero_grad()
@@ -228,6 +268,13 @@ def main():
         device_sync(); ctrl_barrier()
         state["t1"] = time.time(); state["mb1"] = micro_count
         micro = state["mb1"] - state["mb0"]
+        # ddp zeroes its gradients at the end of every step
+        outputs = {"loss": last_loss.float().reshape(1),
+                   "params": params[:n_live]}
+
+    if args.dump_outputs and rank == 0:
+        device_sync()
+        dump_outputs(args.dump_outputs, outputs)
 
     elapsed = state["t1"] - state["t0"]
     tokens_local = micro * args.batch * args.seq
