@@ -61,9 +61,10 @@ class LlamaAttention(nn.Module):
                 hd = cfg.head_dim
                 offs = (0, cfg.num_heads * hd,
                         (cfg.num_heads + cfg.num_kv_heads) * hd)
-                o = AttnQKVPackedFn.apply(qkv, cos, sin, cfg.num_heads,
-                                          cfg.num_kv_heads, hd,
-                                          hd ** -0.5, 0, offs)
+                # rotates qkv's q|k sections in place; returns (o, qkv)
+                o, _ = AttnQKVPackedFn.apply(qkv, cos, sin, cfg.num_heads,
+                                             cfg.num_kv_heads, hd,
+                                             hd ** -0.5, 0, offs)
                 return arena_linear(self.o_proj, o)
             q, k, v = torch.split(qkv, splits, dim=-1)
             q = q.contiguous().view(B, S, cfg.num_heads, cfg.head_dim)

@@ -71,7 +71,7 @@ class RMSNormFn(torch.autograd.Function):
         none = torch.empty(0, device=x.device, dtype=x.dtype)
         dx, dw = ops.hip_ext().rmsnorm_bwd(dy.contiguous(), x,
                                            weight.contiguous(), rstd, none)
-        return dx, dw.to(weight.dtype), None
+        return dx, dw, None
 
 
 class AddRMSNormFn(torch.autograd.Function):
@@ -95,7 +95,7 @@ class AddRMSNormFn(torch.autograd.Function):
         dx, dw = ops.hip_ext().rmsnorm_bwd(dy.contiguous(), s,
                                            weight.contiguous(), rstd, dadd)
         # d(x) == d(res): both inputs feed the same sum
-        return dx, dx, dw.to(weight.dtype), None
+        return dx, dx, dw, None
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -114,7 +114,7 @@ class LayerNormFn(torch.autograd.Function):
         dx, dw, db = ops.hip_ext().layernorm_bwd(dy.contiguous(), x,
                                                  weight.contiguous(), mean,
                                                  rstd, none)
-        return dx, dw.to(weight.dtype), db.to(weight.dtype), None
+        return dx, dw, db, None
 
 
 class AddLayerNormFn(torch.autograd.Function):
@@ -136,7 +136,7 @@ class AddLayerNormFn(torch.autograd.Function):
         dx, dw, db = ops.hip_ext().layernorm_bwd(dy.contiguous(), s,
                                                  weight.contiguous(), mean,
                                                  rstd, dadd)
-        return dx, dx, dw.to(weight.dtype), db.to(weight.dtype), None
+        return dx, dx, dw, db, None
 
 
 class RoPEFn(torch.autograd.Function):
@@ -192,11 +192,17 @@ class CausalLMLossFn(torch.autograd.Function):
 
 class AttnQKVPackedFn(torch.autograd.Function):
     """The whole attention core over the PACKED fused projection output
-    [B, S, (H+2Hkv)·D]: optional RoPE (strided kernel on the q/k sections) +
-    flash attention v4 forward; backward emits one packed grad — no
-    torch.split forward copies, no cat backward. D=64, S%256==0.
-    Section offsets support both packing orders (Llama q|k|v,
-    GPT-Neo k|v|q); window>0 = GPT-Neo local attention."""
+    [B, S, (H+2Hkv)·D]: optional RoPE + flash attention v4 forward; backward
+    emits one packed grad — no torch.split forward copies, no cat backward.
+    D in {64, 128}, S%256==0. Section offsets support both packing orders
+    (Llama q|k|v, GPT-Neo k|v|q); window>0 = GPT-Neo local attention.
+
+    With RoPE the q|k sections of `qkv` are rotated IN PLACE by one launch
+    (the producer, FusedArenaLinearFn, saves only its inputs; the unroped
+    projection is never read again) and the inverse rotation of the grad is
+    folded into the dq kernel's epilogue and the GQA reduce; the call then
+    returns (o, qkv), since a tensor marked dirty has to be an output.
+    Without RoPE (cos is None) it returns o alone."""
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, H, Hkv, D, scale, window, offs):
@@ -206,23 +212,26 @@ class AttnQKVPackedFn(torch.autograd.Function):
         if cos is not None:
             cos = cos.float().contiguous()
             sin = sin.float().contiguous()
-            roped = torch.empty_like(qkv)
-            ext.rope_packed(qkv, roped, cos, sin, q_off, H, D, False)
-            ext.rope_packed(qkv, roped, cos, sin, k_off, Hkv, D, False)
-            roped[..., v_off:v_off + Hkv * D].copy_(
-                qkv[..., v_off:v_off + Hkv * D])
-        else:
-            roped = qkv
+            if qkv._is_view() or (qkv.is_leaf and qkv.requires_grad):
+                # autograd forbids in-place on these: rotate a private copy
+                qkv = qkv.clone()
+            else:
+                ctx.mark_dirty(qkv)
+            ext.rope_qk_inplace(qkv, cos, sin, H, Hkv, D, q_off, k_off)
+        roped = qkv
         o, lse = ext.attn_fwd_packed(roped, H, Hkv, D, float(scale),
                                      int(window or 0), q_off, k_off, v_off)
         ctx.save_for_backward(roped, o, lse,
                               cos if cos is not None else torch.empty(0),
                               sin if sin is not None else torch.empty(0))
         ctx.meta = (H, Hkv, D, float(scale), int(window or 0), offs)
-        return o                     # [B, S, H*D]
+        if cos is None:
+            return o                 # [B, S, H*D]; qkv untouched
+        ctx.set_materialize_grads(False)   # no zeros for the unused output
+        return o, roped
 
     @staticmethod
-    def backward(ctx, dO):
+    def backward(ctx, dO, _droped=None):
         ext = ops.hip_ext()
         roped, o, lse, cos, sin = ctx.saved_tensors
         H, Hkv, D, scale, window, offs = ctx.meta
@@ -231,10 +240,19 @@ class AttnQKVPackedFn(torch.autograd.Function):
         dO = dO.contiguous()
         delta = ext.attn_delta(dO.view(B, S, H, D), o.view(B, S, H, D))
         dqkv = torch.empty_like(roped)
+        rope = cos.numel() > 0
+        # with RoPE the dq kernel rotates its result by -theta in the
+        # epilogue (bit-equal to the stand-alone inverse rope pass)
         dkq, dvq = ext.attn_bwd_packed(roped, dO, lse, delta, dqkv, H, Hkv,
-                                       D, scale, window, q_off, k_off, v_off)
+                                       D, scale, window, q_off, k_off, v_off,
+                                       cos if rope else None,
+                                       sin if rope else None)
         rep = H // Hkv
-        if hasattr(ext, "attn_gqa_reduce"):
+        if rope:
+            # group-sum + inverse rotation of dk + bf16 cast in one pass
+            ext.attn_gqa_reduce_rope(dkq, dvq, dqkv, cos, sin, Hkv, rep, D,
+                                     k_off, v_off)
+        elif hasattr(ext, "attn_gqa_reduce"):
             # one pass: group-sum over the rep query heads + bf16 cast +
             # strided write into the packed grad's k|v sections (replaces
             # two dim-3 sums, two casts and two strided copies per layer)
@@ -247,10 +265,6 @@ class AttnQKVPackedFn(torch.autograd.Function):
         else:
             dqkv[..., k_off:k_off + Hkv * D] = dkq.reshape(B, S, Hkv * D)
             dqkv[..., v_off:v_off + Hkv * D] = dvq.reshape(B, S, Hkv * D)
-        if cos.numel():
-            # inverse rotation in place on the q/k grad sections
-            ext.rope_packed(dqkv, dqkv, cos, sin, q_off, H, D, True)
-            ext.rope_packed(dqkv, dqkv, cos, sin, k_off, Hkv, D, True)
         return (dqkv, None, None, None, None, None, None, None, None)
 
 

@@ -362,7 +362,8 @@ extern "C" void acco_attn_bwd32_dq(const void*, const void*, const void*,
                                    const void*, const float*, const float*,
                                    void*, int, int, int, int, int, float,
                                    int, long long, long long, long long,
-                                   long long, hipStream_t);
+                                   long long, const float*, const float*,
+                                   hipStream_t);
 extern "C" void acco_attn_bwd32_dkv(const void*, const void*, const void*,
                                     const void*, const float*, const float*,
                                     void*, void*, int, int, int, int, int,
@@ -378,7 +379,8 @@ void acco_attn_bwd_dq(const void* q, const void* k, const void* v,
   if ((D == 64 || D == 128) && S % 256 == 0) {
     acco_attn_bwd32_dq(q, k, v, dO, lse, delta, dq, B, S, H, Hkv, D, scale,
                        window, (long long)H * D, (long long)Hkv * D,
-                       (long long)H * D, (long long)H * D, stream);
+                       (long long)H * D, (long long)H * D, nullptr, nullptr,
+                       stream);
     return;
   }
   const bool wide = (S % 128 == 0) && (D == 64);

@@ -122,7 +122,9 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                           u16* __restrict__ dq,
                           int S, int H, int Hkv, float scale, int window,
                           long long q_rs, long long kv_rs, long long do_rs,
-                          long long dq_rs) {
+                          long long dq_rs,
+                          const float* __restrict__ rope_cos,   // [S, D] or
+                          const float* __restrict__ rope_sin) { // null = off
   constexpr int KS = D / 16;
   constexpr int DT = D / 32;
   constexpr int KROW = D + 8;
@@ -233,6 +235,30 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   }
 
   u16* dQp = dq + ((long long)b * S + q0) * dq_rs + (long long)h * D;
+  // Fused inverse RoPE (rotation by -theta): column d = t*32 + lq and its
+  // partner d + D/2 are acc_dq[t][r] / acc_dq[t + DT/2][r] of the SAME lane,
+  // so the rotation is lane-local — the separate read-modify-write pass
+  // over dq disappears. The accumulators are rounded to bf16 first and the
+  // rotation runs on the rounded values, exactly as the stand-alone
+  // rope_kernel<true> pass over the stored dq did: results stay bit-equal.
+  if (rope_cos != nullptr) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const float* cr = rope_cos + (long long)(q0 + qrow) * D + lq;
+      const float* sr = rope_sin + (long long)(q0 + qrow) * D + lq;
+#pragma unroll
+      for (int t = 0; t < DT / 2; ++t) {
+        const float c = cr[t * 32], sn = sr[t * 32];
+        const float g1 = bf16_to_f32(f32_to_bf16(acc_dq[t][r]));
+        const float g2 = bf16_to_f32(f32_to_bf16(acc_dq[t + DT / 2][r]));
+        // explicit contraction, the one rope_kernel<true> compiles to
+        // (sin product rounded, cos product fused)
+        acc_dq[t][r] = __fmaf_rn(g1, c, __fmul_rn(g2, sn));
+        acc_dq[t + DT / 2][r] = __fmaf_rn(g2, c, -__fmul_rn(g1, sn));
+      }
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int qrow = (r & 3) + 8 * (r >> 2) + 4 * hi;
@@ -513,6 +539,7 @@ void acco_attn_bwd32_dq(const void* q, const void* k, const void* v,
                         void* dq, int B, int S, int H, int Hkv, int D,
                         float scale, int window, long long q_rs,
                         long long kv_rs, long long do_rs, long long dq_rs,
+                        const float* rope_cos, const float* rope_sin,
                         hipStream_t stream) {
   dim3 grid(S / BT, B * H);
   const int lds = (2 * KT * (D + 8) + D * LST) * sizeof(u16);
@@ -520,12 +547,14 @@ void acco_attn_bwd32_dq(const void* q, const void* k, const void* v,
     hipLaunchKernelGGL(attn_bwd32_dq_kernel<64>, grid, dim3(512), lds, stream,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv,
-                       scale, window, q_rs, kv_rs, do_rs, dq_rs);
+                       scale, window, q_rs, kv_rs, do_rs, dq_rs, rope_cos,
+                       rope_sin);
   else
     hipLaunchKernelGGL(attn_bwd32_dq_kernel<128>, grid, dim3(512), lds,
                        stream, (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv,
-                       scale, window, q_rs, kv_rs, do_rs, dq_rs);
+                       scale, window, q_rs, kv_rs, do_rs, dq_rs, rope_cos,
+                       rope_sin);
 }
 
 void acco_attn_bwd32_dkv(const void* q, const void* k, const void* v,

@@ -21,6 +21,8 @@ extern "C" void acco_gelu_bwd(const void*, const void*, void*, long long,
 extern "C" void acco_rmsnorm_fwd(const void*, const void*, void*, void*,
                                  const void*, void*,
                                  long long, int, float, hipStream_t);
+extern "C" void acco_norm_dw_finalize(const float*, const float*, void*, void*,
+                                      int, int, bool, hipStream_t);
 extern "C" void acco_rmsnorm_bwd(const void*, const void*, const void*,
                                  const void*, void*, void*, const void*,
                                  long long, int, hipStream_t);
@@ -37,6 +39,9 @@ extern "C" void acco_layernorm_bwd(const void*, const void*, const void*,
 extern "C" void acco_rope(const void*, void*, const float*, const float*,
                           long long, int, int, int, bool, long long,
                           hipStream_t);
+extern "C" void acco_rope_qk_inplace(void*, const float*, const float*,
+                                     long long, int, int, int, int, long long,
+                                     long long, long long, hipStream_t);
 extern "C" void acco_ce_fwd(const void*, const long long*, float*, float*,
                             long long, int, int, float, hipStream_t);
 extern "C" void acco_ce_bwd(const void*, const long long*, const float*,
@@ -54,7 +59,8 @@ extern "C" void acco_attn_bwd32_dq(const void*, const void*, const void*,
                                    const void*, const float*, const float*,
                                    void*, int, int, int, int, int, float,
                                    int, long long, long long, long long,
-                                   long long, hipStream_t);
+                                   long long, const float*, const float*,
+                                   hipStream_t);
 extern "C" void acco_attn_bwd32_dkv(const void*, const void*, const void*,
                                     const void*, const float*, const float*,
                                     void*, void*, int, int, int, int, int,
@@ -69,6 +75,11 @@ extern "C" void acco_attn_delta(const void*, const void*, float*, long long,
 extern "C" void acco_attn_gqa_reduce(const void*, const void*, void*,
                                      long long, int, int, int, long long,
                                      long long, long long, hipStream_t);
+extern "C" void acco_attn_gqa_reduce_rope(const void*, const void*, void*,
+                                          const float*, const float*,
+                                          long long, int, int, int, int,
+                                          long long, long long, long long,
+                                          hipStream_t);
 extern "C" void acco_attn_bwd_dkv(const void*, const void*, const void*,
                                   const void*, const float*, const float*,
                                   void*, void*, int, int, int, int, int,
@@ -127,6 +138,19 @@ at::Tensor colsum(at::Tensor in) {
 
 static hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStream().stream();
+}
+
+// fp32 [>=S, D] contiguous cos/sin tables on the same device as `like`
+static void check_rope_table(const at::Tensor& cos_t, const at::Tensor& sin_t,
+                             int64_t S, int64_t D, const at::Tensor& like) {
+  TORCH_CHECK(cos_t.is_cuda() && sin_t.is_cuda() &&
+              cos_t.device() == like.device() &&
+              sin_t.device() == like.device());
+  TORCH_CHECK(cos_t.scalar_type() == at::kFloat && cos_t.is_contiguous() &&
+              sin_t.scalar_type() == at::kFloat && sin_t.is_contiguous());
+  TORCH_CHECK(cos_t.dim() == 2 && cos_t.size(0) >= S && cos_t.size(1) == D &&
+              sin_t.sizes() == cos_t.sizes(),
+              "cos/sin must be fp32 [>=S, D]");
 }
 
 // ---- SwiGLU / gelu_new
@@ -240,7 +264,12 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                    rstd.data_ptr(), dx.data_ptr(), dw_part.data_ptr(),
                    (dadd.defined() && dadd.numel() > 0) ? dadd.data_ptr() : nullptr, R, D,
                    cur_stream());
-  return {dx, colsum(dw_part)};
+  // one launch: partial rows → dW in the weight's dtype (no zero-fill, no
+  // atomics, no cast)
+  auto dw = at::empty({D}, w.options());
+  acco_norm_dw_finalize(dw_part.data_ptr<float>(), nullptr, dw.data_ptr(),
+                        nullptr, grid, D, true, cur_stream());
+  return {dx, dw};
 }
 
 // ---- LayerNorm
@@ -296,7 +325,12 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x,
                      dw_part.data_ptr(), db_part.data_ptr(),
                      (dadd.defined() && dadd.numel() > 0) ? dadd.data_ptr() : nullptr, R, D,
                      cur_stream());
-  return {dx, colsum(dw_part), colsum(db_part)};
+  auto dw = at::empty({D}, w.options());
+  auto db = at::empty({D}, w.options());
+  acco_norm_dw_finalize(dw_part.data_ptr<float>(), db_part.data_ptr<float>(),
+                        dw.data_ptr(), db.data_ptr(), grid, D, true,
+                        cur_stream());
+  return {dx, dw, db};
 }
 
 // ---- RoPE ([B, S, H, D] contiguous)
@@ -427,11 +461,39 @@ void attn_gqa_reduce(at::Tensor dkq, at::Tensor dvq, at::Tensor dqkv,
                      int64_t v_off) {
   CHECK_BF16_CONTIG(dkq); CHECK_BF16_CONTIG(dvq); CHECK_BF16_CONTIG(dqkv);
   TORCH_CHECK(D % 8 == 0);
+  TORCH_CHECK(dkq.dim() == 4 && dvq.sizes() == dkq.sizes() &&
+              dkq.size(-1) * dkq.size(-2) == Hkv * rep * D,
+              "dkq/dvq must be [B, S, Hkv*rep, D]");
   const long long T = dkq.size(0) * dkq.size(1);
   const long long W = dqkv.size(2);
   acco_attn_gqa_reduce(dkq.data_ptr(), dvq.data_ptr(), dqkv.data_ptr(), T,
                        (int)Hkv, (int)rep, (int)D, W, k_off, v_off,
                        cur_stream());
+}
+
+// same reduce with the inverse RoPE of the k grad folded in (rep >= 1)
+void attn_gqa_reduce_rope(at::Tensor dkq, at::Tensor dvq, at::Tensor dqkv,
+                          at::Tensor cos_t, at::Tensor sin_t, int64_t Hkv,
+                          int64_t rep, int64_t D, int64_t k_off,
+                          int64_t v_off) {
+  CHECK_BF16_CONTIG(dkq); CHECK_BF16_CONTIG(dvq); CHECK_BF16_CONTIG(dqkv);
+  TORCH_CHECK(dkq.dim() == 4 && dvq.sizes() == dkq.sizes() &&
+              dkq.size(-1) * dkq.size(-2) == Hkv * rep * D,
+              "dkq/dvq must be [B, S, Hkv*rep, D]");
+  TORCH_CHECK(dqkv.dim() == 3 && dqkv.size(0) == dkq.size(0) &&
+              dqkv.size(1) == dkq.size(1));
+  const long long T = dkq.size(0) * dkq.size(1);
+  const int S = (int)dkq.size(1);
+  const long long W = dqkv.size(2);
+  TORCH_CHECK(D % 16 == 0 && W % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 &&
+              k_off >= 0 && v_off >= 0 && k_off + Hkv * D <= W &&
+              v_off + Hkv * D <= W);
+  check_rope_table(cos_t, sin_t, S, D, dqkv);
+  TORCH_CHECK(T * Hkv * (D / 16) < (1LL << 31));
+  acco_attn_gqa_reduce_rope(dkq.data_ptr(), dvq.data_ptr(), dqkv.data_ptr(),
+                            cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
+                            T, S, (int)Hkv, (int)rep, (int)D, W, k_off, v_off,
+                            cur_stream());
 }
 
 // ---- experimental NT GEMM (C = A · B^T, bf16; bench/refcheck only)
@@ -463,6 +525,28 @@ std::vector<at::Tensor> rope_packed(at::Tensor src, at::Tensor dst,
   return {dst};
 }
 
+// forward rotation of the q and k sections of the packed projection output
+// IN PLACE, one launch; the V section is left untouched
+void rope_qk_inplace(at::Tensor qkv, at::Tensor cos_t, at::Tensor sin_t,
+                     int64_t H, int64_t Hkv, int64_t D, int64_t q_off,
+                     int64_t k_off) {
+  CHECK_BF16_CONTIG(qkv);
+  TORCH_CHECK(qkv.dim() == 3);
+  const long long T = qkv.size(0) * qkv.size(1);
+  const int S = (int)qkv.size(1);
+  const long long W = qkv.size(2);
+  TORCH_CHECK(D % 16 == 0 && W % 8 == 0 && q_off % 8 == 0 && k_off % 8 == 0 &&
+              q_off >= 0 && k_off >= 0 && q_off + H * D <= W &&
+              k_off + Hkv * D <= W);
+  TORCH_CHECK(q_off + H * D <= k_off || k_off + Hkv * D <= q_off,
+              "q and k sections overlap");
+  check_rope_table(cos_t, sin_t, S, D, qkv);
+  TORCH_CHECK(T * (H + Hkv) * (D / 16) < (1LL << 31));
+  acco_rope_qk_inplace(qkv.data_ptr(), cos_t.data_ptr<float>(),
+                       sin_t.data_ptr<float>(), T, S, (int)H, (int)Hkv,
+                       (int)D, W, q_off, k_off, cur_stream());
+}
+
 std::vector<at::Tensor> attn_fwd_packed(at::Tensor qkv, int64_t H,
                                         int64_t Hkv, int64_t D, double scale,
                                         int64_t window, int64_t q_off,
@@ -485,10 +569,21 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
                                         at::Tensor dqkv, int64_t H,
                                         int64_t Hkv, int64_t D, double scale,
                                         int64_t window, int64_t q_off,
-                                        int64_t k_off, int64_t v_off) {
+                                        int64_t k_off, int64_t v_off,
+                                        c10::optional<at::Tensor> cos_opt,
+                                        c10::optional<at::Tensor> sin_opt) {
   CHECK_BF16_CONTIG(qkv); CHECK_BF16_CONTIG(dO); CHECK_BF16_CONTIG(dqkv);
   const int B = (int)qkv.size(0), S = (int)qkv.size(1);
   const long long W = qkv.size(2);
+  // cos/sin given: the dq kernel applies the inverse RoPE in its epilogue
+  const float* rc = nullptr;
+  const float* rs = nullptr;
+  if (cos_opt.has_value() && cos_opt->defined() && cos_opt->numel() > 0) {
+    TORCH_CHECK(sin_opt.has_value() && sin_opt->defined());
+    check_rope_table(*cos_opt, *sin_opt, S, D, qkv);
+    rc = cos_opt->data_ptr<float>();
+    rs = sin_opt->data_ptr<float>();
+  }
   const u16* base = (const u16*)qkv.data_ptr();
   u16* dbase = (u16*)dqkv.data_ptr();
   // dq straight into the packed grad (stride W); dk/dv per-QUERY-head temps
@@ -497,7 +592,7 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
   acco_attn_bwd32_dq(base + q_off, base + k_off, base + v_off, dO.data_ptr(),
                      lse.data_ptr<float>(), delta.data_ptr<float>(),
                      dbase + q_off, B, S, (int)H, (int)Hkv, (int)D,
-                     (float)scale, (int)window, W, W, H * D, W,
+                     (float)scale, (int)window, W, W, H * D, W, rc, rs,
                      cur_stream());
   acco_attn_bwd32_dkv(base + q_off, base + k_off, base + v_off,
                       dO.data_ptr(), lse.data_ptr<float>(),
@@ -542,9 +637,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_delta", &attn_delta);
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_gqa_reduce", &attn_gqa_reduce);
+  m.def("attn_gqa_reduce_rope", &attn_gqa_reduce_rope);
+  m.def("rope_qk_inplace", &rope_qk_inplace);
   m.def("gemm_nt", &gemm_nt);
   m.def("rope_packed", &rope_packed);
   m.def("attn_fwd_packed", &attn_fwd_packed);
-  m.def("attn_bwd_packed", &attn_bwd_packed);
+  m.def("attn_bwd_packed", &attn_bwd_packed, py::arg("qkv"), py::arg("dO"),
+        py::arg("lse"), py::arg("delta"), py::arg("dqkv"), py::arg("H"),
+        py::arg("Hkv"), py::arg("D"), py::arg("scale"), py::arg("window"),
+        py::arg("q_off"), py::arg("k_off"), py::arg("v_off"),
+        py::arg("cos") = py::none(), py::arg("sin") = py::none());
   m.attr("_gfx950") = true;
 }

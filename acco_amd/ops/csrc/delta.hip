@@ -147,7 +147,95 @@ __global__ void gqa_reduce_kernel(const u16* __restrict__ dkq,
   }
 }
 
+ACCO_DEV void acc8(const u16* p, float* f) {
+  const uint4 v = *reinterpret_cast<const uint4*>(p);
+  const u16* u = reinterpret_cast<const u16*>(&v);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) f[i] += bf16_to_f32(u[i]);
+}
+
+ACCO_DEV void put8(u16* p, const float* f) {
+  uint4 v;
+  u16* u = reinterpret_cast<u16*>(&v);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) u[i] = f32_to_bf16(f[i]);
+  *reinterpret_cast<uint4*>(p) = v;
+}
+
+// Rotating variant of gqa_reduce_kernel: the inverse RoPE of the k grad is
+// folded into the group-sum. One thread owns the 8-column chunk at d AND
+// the chunk at d + D/2 of one kv head, sums both over the rep query heads
+// in fp32, rotates the (bf16-rounded) k pair by -theta (dk1 = g1·cos +
+// g2·sin, dk2 = g2·cos − g1·sin) and stores bf16; the v chunks are summed
+// and written unrotated. Replaces the read-modify-write rope pass over the
+// k section that followed the plain reduce.
+__global__ __launch_bounds__(256)
+void gqa_reduce_rope_kernel(const u16* __restrict__ dkq,
+                            const u16* __restrict__ dvq,
+                            u16* __restrict__ dqkv,
+                            const float* __restrict__ cos_t,
+                            const float* __restrict__ sin_t,
+                            unsigned total,   // T*Hkv*(D/16)
+                            unsigned Hkv, unsigned rep, unsigned D,
+                            unsigned S, long long W,
+                            long long k_off, long long v_off) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= total) return;
+  const unsigned cph = D / 16, ipt = Hkv * cph;
+  const unsigned t = i / ipt, r0 = i % ipt;
+  const unsigned hkv = r0 / cph, c8 = (r0 % cph) * 8;
+  const unsigned s = t % S;
+  const long long in_base =
+      ((long long)t * Hkv * rep + (long long)hkv * rep) * D + c8;
+  float k1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, k2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float v1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, v2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (unsigned r = 0; r < rep; ++r) {
+    const u16* pk = dkq + in_base + (long long)r * D;
+    const u16* pv = dvq + in_base + (long long)r * D;
+    acc8(pk, k1); acc8(pk + D / 2, k2);
+    acc8(pv, v1); acc8(pv + D / 2, v2);
+  }
+  const float* cp = cos_t + (size_t)s * D + c8;
+  const float* sp = sin_t + (size_t)s * D + c8;
+  const float4 c0 = reinterpret_cast<const float4*>(cp)[0];
+  const float4 c1 = reinterpret_cast<const float4*>(cp)[1];
+  const float4 s0 = reinterpret_cast<const float4*>(sp)[0];
+  const float4 s1 = reinterpret_cast<const float4*>(sp)[1];
+  const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+  const float ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+  float o1[8], o2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    // round the group sums to bf16 first, as the plain reduce stores them,
+    // so the result is bit-equal to reduce + stand-alone inverse rope
+    const float a = bf16_to_f32(f32_to_bf16(k1[j]));
+    const float b = bf16_to_f32(f32_to_bf16(k2[j]));
+    // explicit contraction, the one rope_kernel<true> compiles to
+    o1[j] = __fmaf_rn(a, cc[j], __fmul_rn(b, ss[j]));
+    o2[j] = __fmaf_rn(b, cc[j], -__fmul_rn(a, ss[j]));
+  }
+  u16* ok = dqkv + (long long)t * W + k_off + (long long)hkv * D + c8;
+  u16* ov = dqkv + (long long)t * W + v_off + (long long)hkv * D + c8;
+  put8(ok, o1); put8(ok + D / 2, o2);
+  put8(ov, v1); put8(ov + D / 2, v2);
+}
+
 }  // namespace
+
+extern "C" void acco_attn_gqa_reduce_rope(const void* dkq, const void* dvq,
+                                          void* dqkv, const float* cos_t,
+                                          const float* sin_t, long long T,
+                                          int S, int Hkv, int rep, int D,
+                                          long long W, long long k_off,
+                                          long long v_off,
+                                          hipStream_t stream) {
+  const unsigned total = (unsigned)(T * Hkv * (D / 16));
+  if (total == 0) return;
+  hipLaunchKernelGGL(gqa_reduce_rope_kernel, dim3((total + 255) / 256),
+                     dim3(256), 0, stream, (const u16*)dkq, (const u16*)dvq,
+                     (u16*)dqkv, cos_t, sin_t, total, (unsigned)Hkv,
+                     (unsigned)rep, (unsigned)D, (unsigned)S, W, k_off, v_off);
+}
 
 extern "C" void acco_attn_gqa_reduce(const void* dkq, const void* dvq,
                                      void* dqkv, long long T, int Hkv,

@@ -11,8 +11,8 @@
 // scratch — a first version with a runtime chunk loop ran 8-14× off
 // roofline; see profiles/r01_bench_llama1b_acco_1gpu_kernels.txt).
 // dW/dB land as one [partial_rows, D] fp32 scratch row per (block, group)
-// reduced by a tiny torch sum in the wrapper (atomicAdd serialized ~3×
-// worse).
+// reduced to [D] in the weight's dtype by norm_dw_finalize_kernel (one
+// launch; atomicAdd from the bwd kernels serialized ~3× worse).
 // Replaces the HF RMSNorm / nn.LayerNorm ATen chains.
 
 #include "common.h"
@@ -661,6 +661,68 @@ void colsum_kernel(const Tin* __restrict__ in, float* __restrict__ out,
     if (d0 + k < D) atomicAdd(out + d0 + k, acc[k]);
 }
 
+// ------------------------------------- norm dW/dB partial-row finalize
+// out[d] = Tw(Σ_p part[p·D + d]) for the [P, D] fp32 scratch the bwd
+// kernels emit, written straight in the weight's dtype. A block owns 32
+// columns (one 128-byte line per partial row) and walks ALL P rows with 32
+// row slots × float4 lanes, then folds the slots through LDS — no atomics,
+// so no zero-fill of the output and no separate cast launch (the colsum
+// tail was at::zeros + colsum_kernel<float> + a bf16 cast per norm).
+// blockIdx.y picks the (in, out) pair so LayerNorm's dW and dB share one
+// launch.
+constexpr int FIN_COLS = 32;              // columns per block
+constexpr int FIN_SLOTS = BLOCK / (FIN_COLS / 4);   // 32 row slots
+
+__global__ __launch_bounds__(BLOCK)
+void norm_dw_finalize_kernel(const float* __restrict__ in0,
+                             const float* __restrict__ in1,
+                             void* __restrict__ out0, void* __restrict__ out1,
+                             int P, int D, int out_bf16) {
+  __shared__ float red[FIN_SLOTS][FIN_COLS + 4];
+  const float* in = blockIdx.y == 0 ? in0 : in1;
+  void* out = blockIdx.y == 0 ? out0 : out1;
+  const int cx = threadIdx.x % (FIN_COLS / 4);
+  const int slot = threadIdx.x / (FIN_COLS / 4);
+  const int d0 = blockIdx.x * FIN_COLS + cx * 4;     // D % 8 == 0
+  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
+  if (d0 < D) {
+    const float* col = in + d0;
+    int p = slot;
+    for (; p + 3 * FIN_SLOTS < P; p += 4 * FIN_SLOTS) {
+      const float4 v0 = *reinterpret_cast<const float4*>(col + (long long)p * D);
+      const float4 v1 = *reinterpret_cast<const float4*>(
+          col + (long long)(p + FIN_SLOTS) * D);
+      const float4 v2 = *reinterpret_cast<const float4*>(
+          col + (long long)(p + 2 * FIN_SLOTS) * D);
+      const float4 v3 = *reinterpret_cast<const float4*>(
+          col + (long long)(p + 3 * FIN_SLOTS) * D);
+      a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
+      a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
+      a2.x += v2.x; a2.y += v2.y; a2.z += v2.z; a2.w += v2.w;
+      a3.x += v3.x; a3.y += v3.y; a3.z += v3.z; a3.w += v3.w;
+    }
+    for (; p < P; p += FIN_SLOTS) {
+      const float4 v0 = *reinterpret_cast<const float4*>(col + (long long)p * D);
+      a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
+    }
+  }
+  red[slot][cx * 4 + 0] = (a0.x + a1.x) + (a2.x + a3.x);
+  red[slot][cx * 4 + 1] = (a0.y + a1.y) + (a2.y + a3.y);
+  red[slot][cx * 4 + 2] = (a0.z + a1.z) + (a2.z + a3.z);
+  red[slot][cx * 4 + 3] = (a0.w + a1.w) + (a2.w + a3.w);
+  __syncthreads();
+  if (threadIdx.x < FIN_COLS) {
+    const int d = blockIdx.x * FIN_COLS + threadIdx.x;
+    float sum = 0.0f;
+#pragma unroll
+    for (int sl = 0; sl < FIN_SLOTS; ++sl) sum += red[sl][threadIdx.x];
+    if (d < D) {
+      if (out_bf16) reinterpret_cast<u16*>(out)[d] = f32_to_bf16(sum);
+      else reinterpret_cast<float*>(out)[d] = sum;
+    }
+  }
+}
+
 int groups_for(int D) {
   const int nv = D / VEC;
   if (nv <= 64) return 4;      // one wave per row
@@ -702,6 +764,15 @@ int wr_blocks(long long R) {
 }  // namespace
 
 extern "C" {
+
+// dW (and optionally dB) partial rows [P, D] fp32 → [D] in the weight dtype
+void acco_norm_dw_finalize(const float* dw_part, const float* db_part,
+                           void* dw, void* db, int P, int D, bool out_bf16,
+                           hipStream_t s) {
+  dim3 grid((D + FIN_COLS - 1) / FIN_COLS, db_part != nullptr ? 2 : 1);
+  hipLaunchKernelGGL(norm_dw_finalize_kernel, grid, dim3(BLOCK), 0, s,
+                     dw_part, db_part, dw, db, P, D, out_bf16 ? 1 : 0);
+}
 
 void acco_colsum(const void* in, float* out, long long P, int D,
                  bool in_is_bf16, hipStream_t s) {
