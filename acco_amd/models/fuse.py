@@ -63,10 +63,10 @@ def _acc_wgrad(g_view, d2t, x2):
 def _acc_bias_grad(g_b, d2):
     """db += column-sum of d2. Measured same-box: ATen's sum(0)+add wins
     here (GPT-Neo 409.7k vs 361.8k tokens/s with the colsum+cast+add
-    chain — the bias case is many small launches, not bandwidth), while
-    colsum stays the winner for the norm bwd dW/dB partial reduces inside
-    the extension (fewer, larger, fp32). ACCO_COLSUM_BIAS=1 re-enables the
-    kernel path for re-measurement."""
+    chain — the bias case is many small launches, not bandwidth). The norm
+    bwd dW/dB partial rows do not come through here: the extension reduces
+    them itself with norm_dw_finalize_kernel. ACCO_COLSUM_BIAS=1 re-enables
+    the kernel path for re-measurement."""
     from acco_amd import ops as _ops
     if (d2.is_cuda and _ops.have_kernel("colsum")
             and os.environ.get("ACCO_COLSUM_BIAS") == "1"):

@@ -34,6 +34,7 @@ def _check_fresh(mod) -> None:
     stale = [os.path.basename(f)
              for f in glob.glob(os.path.join(csrc, "*.hip"))
              + glob.glob(os.path.join(csrc, "*.cpp"))
+             + glob.glob(os.path.join(csrc, "*.h"))
              if not f.endswith("_hip.hip") and os.path.getmtime(f) > so_mtime]
     if stale:
         warnings.warn(

@@ -68,9 +68,8 @@ class RMSNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight, rstd = ctx.saved_tensors
-        none = torch.empty(0, device=x.device, dtype=x.dtype)
         dx, dw = ops.hip_ext().rmsnorm_bwd(dy.contiguous(), x,
-                                           weight.contiguous(), rstd, none)
+                                           weight.contiguous(), rstd, None)
         return dx, dw, None
 
 
@@ -90,8 +89,7 @@ class AddRMSNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, ds):
         s, weight, rstd = ctx.saved_tensors
-        dadd = (ds.contiguous() if ds is not None
-                else torch.empty(0, device=s.device, dtype=s.dtype))
+        dadd = ds.contiguous() if ds is not None else None
         dx, dw = ops.hip_ext().rmsnorm_bwd(dy.contiguous(), s,
                                            weight.contiguous(), rstd, dadd)
         # d(x) == d(res): both inputs feed the same sum
@@ -110,10 +108,9 @@ class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, weight, mean, rstd = ctx.saved_tensors
-        none = torch.empty(0, device=x.device, dtype=x.dtype)
         dx, dw, db = ops.hip_ext().layernorm_bwd(dy.contiguous(), x,
                                                  weight.contiguous(), mean,
-                                                 rstd, none)
+                                                 rstd, None)
         return dx, dw, db, None
 
 
@@ -131,8 +128,7 @@ class AddLayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, ds):
         s, weight, mean, rstd = ctx.saved_tensors
-        dadd = (ds.contiguous() if ds is not None
-                else torch.empty(0, device=s.device, dtype=s.dtype))
+        dadd = ds.contiguous() if ds is not None else None
         dx, dw, db = ops.hip_ext().layernorm_bwd(dy.contiguous(), s,
                                                  weight.contiguous(), mean,
                                                  rstd, dadd)

@@ -16,6 +16,7 @@
 // float4 / bf16x4 accesses per guide Guideline 13.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 

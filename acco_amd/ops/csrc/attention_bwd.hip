@@ -18,6 +18,7 @@
 // per-wave LDS round trip.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -357,18 +358,6 @@ void attn_bwd_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 }
 
 }  // namespace
-
-extern "C" void acco_attn_bwd32_dq(const void*, const void*, const void*,
-                                   const void*, const float*, const float*,
-                                   void*, int, int, int, int, int, float,
-                                   int, long long, long long, long long,
-                                   long long, const float*, const float*,
-                                   hipStream_t);
-extern "C" void acco_attn_bwd32_dkv(const void*, const void*, const void*,
-                                    const void*, const float*, const float*,
-                                    void*, void*, int, int, int, int, int,
-                                    float, int, long long, long long,
-                                    long long, hipStream_t);
 
 extern "C" {
 

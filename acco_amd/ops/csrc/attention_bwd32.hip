@@ -13,6 +13,7 @@
 //               dV += P^T·dO and dK += dS^T·Q via the same redistribution.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 

@@ -19,6 +19,7 @@
 // - causal + optional local window (GPT-Neo 256) + GQA; saves lse.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 
@@ -237,12 +238,6 @@ void attn_fwd_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 }
 
 }  // namespace
-
-extern "C" void acco_attn_fwd32(const void* q, const void* k, const void* v,
-                                void* o, float* lse, int B, int S, int H,
-                                int Hkv, int D, float scale, int window,
-                                long long q_rs, long long kv_rs,
-                                long long o_rs, hipStream_t stream);
 
 extern "C" void acco_attn_fwd(const void* q, const void* k, const void* v,
                               void* o, float* lse, int B, int S, int H,

@@ -14,6 +14,7 @@
 // - D = 64 and S % 256 == 0 only (the dispatch falls back to v3 else).
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 

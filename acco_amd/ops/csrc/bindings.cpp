@@ -1,89 +1,11 @@
 // Python bindings for the acco_amd gfx950 HIP kernels.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 
 #include <hip/hip_runtime.h>
 
-extern "C" void acco_fused_adamw_launch(
-    void* p, const void* g, void* m, void* v, void* out,
-    const float* scale_dev,
-    long long n, bool buf_is_bf16, bool commit,
-    float scale, float lr, float beta1, float beta2, float eps,
-    float weight_decay, long long step_plus_1, hipStream_t stream);
-extern "C" void acco_swiglu_fwd(const void*, const void*, void*, long long,
-                                int, long long, hipStream_t);
-extern "C" void acco_swiglu_bwd(const void*, const void*, const void*, void*,
-                                void*, long long, int, long long,
-                                hipStream_t);
-extern "C" void acco_gelu_fwd(const void*, void*, long long, hipStream_t);
-extern "C" void acco_gelu_bwd(const void*, const void*, void*, long long,
-                              hipStream_t);
-extern "C" void acco_rmsnorm_fwd(const void*, const void*, void*, void*,
-                                 const void*, void*,
-                                 long long, int, float, hipStream_t);
-extern "C" void acco_norm_dw_finalize(const float*, const float*, void*, void*,
-                                      int, int, bool, hipStream_t);
-extern "C" void acco_rmsnorm_bwd(const void*, const void*, const void*,
-                                 const void*, void*, void*, const void*,
-                                 long long, int, hipStream_t);
-extern "C" int acco_norm_bwd_grid(long long R, int D);
-extern "C" void acco_colsum(const void*, float*, long long, int, bool,
-                            hipStream_t);
-extern "C" void acco_layernorm_fwd(const void*, const void*, const void*,
-                                   void*, void*, void*, const void*, void*,
-                                   long long, int, float, hipStream_t);
-extern "C" void acco_layernorm_bwd(const void*, const void*, const void*,
-                                   const void*, const void*, void*, void*,
-                                   void*, const void*, long long, int,
-                                   hipStream_t);
-extern "C" void acco_rope(const void*, void*, const float*, const float*,
-                          long long, int, int, int, bool, long long,
-                          hipStream_t);
-extern "C" void acco_rope_qk_inplace(void*, const float*, const float*,
-                                     long long, int, int, int, int, long long,
-                                     long long, long long, hipStream_t);
-extern "C" void acco_ce_fwd(const void*, const long long*, float*, float*,
-                            long long, int, int, float, hipStream_t);
-extern "C" void acco_ce_bwd(const void*, const long long*, const float*,
-                            void*, const float*, float, const float*,
-                            long long, int, int, float, hipStream_t);
-extern "C" void acco_gemm_nt(const void*, const void*, void*, int, int,
-                             int, hipStream_t);
-extern "C" void acco_attn_fwd(const void*, const void*, const void*, void*,
-                              float*, int, int, int, int, int, float, int,
-                              hipStream_t);
-extern "C" void acco_attn_fwd32(const void*, const void*, const void*, void*,
-                                float*, int, int, int, int, int, float, int,
-                                long long, long long, long long, hipStream_t);
-extern "C" void acco_attn_bwd32_dq(const void*, const void*, const void*,
-                                   const void*, const float*, const float*,
-                                   void*, int, int, int, int, int, float,
-                                   int, long long, long long, long long,
-                                   long long, const float*, const float*,
-                                   hipStream_t);
-extern "C" void acco_attn_bwd32_dkv(const void*, const void*, const void*,
-                                    const void*, const float*, const float*,
-                                    void*, void*, int, int, int, int, int,
-                                    float, int, long long, long long,
-                                    long long, hipStream_t);
-extern "C" void acco_attn_bwd_dq(const void*, const void*, const void*,
-                                 const void*, const float*, const float*,
-                                 void*, int, int, int, int, int, float, int,
-                                 hipStream_t);
-extern "C" void acco_attn_delta(const void*, const void*, float*, long long,
-                                int, int, int, hipStream_t);
-extern "C" void acco_attn_gqa_reduce(const void*, const void*, void*,
-                                     long long, int, int, int, long long,
-                                     long long, long long, hipStream_t);
-extern "C" void acco_attn_gqa_reduce_rope(const void*, const void*, void*,
-                                          const float*, const float*,
-                                          long long, int, int, int, int,
-                                          long long, long long, long long,
-                                          hipStream_t);
-extern "C" void acco_attn_bwd_dkv(const void*, const void*, const void*,
-                                  const void*, const float*, const float*,
-                                  void*, void*, int, int, int, int, int,
-                                  float, int, hipStream_t);
+#include "kernels.h"
 
 namespace {
 
@@ -220,116 +142,141 @@ at::Tensor gelu_bwd(at::Tensor dout, at::Tensor x) {
   return dx;
 }
 
-// ---- RMSNorm
-std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
+// ---- RMSNorm / LayerNorm
+struct NormShape { long long R; int D; };
+
+// The argument contract of every norm entry point, forward and backward:
+// D % 8 == 0 (16-byte vector loads), D <= 16384 (8 chunks of 256 lanes),
+// whole rows; each `like_x` that is given (dy, res, dadd) is bf16 of x's
+// numel on x's device; every saved row statistic is a contiguous fp32 [R]
+// on x's device.
+static NormShape check_norm_args(
+    const at::Tensor& x, const at::Tensor& w,
+    std::initializer_list<c10::optional<at::Tensor>> like_x,
+    std::initializer_list<at::Tensor> stats = {}) {
   CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(w);
-  const int D = (int)w.numel();
-  TORCH_CHECK(D % 8 == 0 && D <= 16384 && x.numel() % D == 0);
+  const long long D = w.numel();
+  TORCH_CHECK(D > 0 && D % 8 == 0 && D <= 16384 && x.numel() % D == 0 &&
+              w.device() == x.device(),
+              "norm width must be a multiple of 8, at most 16384, and divide "
+              "x.numel(); got D=", D, " x.numel()=", x.numel());
   const long long R = x.numel() / D;
+  for (const auto& t : like_x)
+    if (t.has_value()) {
+      CHECK_BF16_CONTIG(*t);
+      TORCH_CHECK(t->numel() == x.numel() && t->device() == x.device(),
+                  "dy/res/dadd must have x's numel and device");
+    }
+  for (const at::Tensor& st : stats)
+    TORCH_CHECK(st.is_cuda() && st.device() == x.device() &&
+                st.scalar_type() == at::kFloat && st.is_contiguous() &&
+                st.numel() == R,
+                "mean/rstd must be contiguous CUDA fp32 with one element per "
+                "row (", R, "), got ", st.numel());
+  return {R, (int)D};
+}
+
+static const void* ptr_or_null(const c10::optional<at::Tensor>& t) {
+  return t.has_value() ? t->data_ptr() : nullptr;
+}
+
+// res given: fused residual add, s = bf16(x + res), y = rmsnorm(s)·w
+static std::vector<at::Tensor> rmsnorm_fwd_impl(
+    const at::Tensor& x, const c10::optional<at::Tensor>& res,
+    const at::Tensor& w, double eps) {
+  const auto [R, D] = check_norm_args(x, w, {res});
   auto y = at::empty_like(x);
   auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
+  at::Tensor sum_out = res.has_value() ? at::empty_like(x) : at::Tensor();
   acco_rmsnorm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), rstd.data_ptr(),
-                   nullptr, nullptr, R, D, (float)eps, cur_stream());
+                   ptr_or_null(res),
+                   res.has_value() ? sum_out.data_ptr() : nullptr, R, D,
+                   (float)eps, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  if (res.has_value()) return {y, sum_out, rstd};
   return {y, rstd};
 }
 
-// fused residual add + RMSNorm: s = bf16(x + res), y = rmsnorm(s)·w
+std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
+  return rmsnorm_fwd_impl(x, c10::nullopt, w, eps);
+}
+
 std::vector<at::Tensor> add_rmsnorm_fwd(at::Tensor x, at::Tensor res,
                                         at::Tensor w, double eps) {
-  CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(res); CHECK_BF16_CONTIG(w);
-  const int D = (int)w.numel();
-  TORCH_CHECK(D % 8 == 0 && D <= 16384 && x.numel() % D == 0);
-  TORCH_CHECK(res.numel() == x.numel());
-  const long long R = x.numel() / D;
-  auto y = at::empty_like(x);
-  auto sum_out = at::empty_like(x);
-  auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
-  acco_rmsnorm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), rstd.data_ptr(),
-                   res.data_ptr(), sum_out.data_ptr(), R, D, (float)eps,
-                   cur_stream());
-  return {y, sum_out, rstd};
+  return rmsnorm_fwd_impl(x, res, w, eps);
 }
 
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                                     at::Tensor rstd,
-                                    c10::optional<at::Tensor> dadd_opt) {
-  at::Tensor dadd = dadd_opt.value_or(at::Tensor());
-  CHECK_BF16_CONTIG(dy); CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(w);
-  const int D = (int)w.numel();
-  const long long R = x.numel() / D;
+                                    c10::optional<at::Tensor> dadd) {
+  const auto [R, D] = check_norm_args(x, w, {dy, dadd}, {rstd});
   auto dx = at::empty_like(x);
   const int grid = acco_norm_bwd_grid(R, D);
   auto dw_part = at::empty({grid, D}, x.options().dtype(at::kFloat));
   acco_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
                    rstd.data_ptr(), dx.data_ptr(), dw_part.data_ptr(),
-                   (dadd.defined() && dadd.numel() > 0) ? dadd.data_ptr() : nullptr, R, D,
-                   cur_stream());
+                   ptr_or_null(dadd), R, D, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   // one launch: partial rows → dW in the weight's dtype (no zero-fill, no
   // atomics, no cast)
   auto dw = at::empty({D}, w.options());
   acco_norm_dw_finalize(dw_part.data_ptr<float>(), nullptr, dw.data_ptr(),
                         nullptr, grid, D, true, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dx, dw};
 }
 
-// ---- LayerNorm
-std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
-                                      double eps) {
-  CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(w); CHECK_BF16_CONTIG(b);
-  const int D = (int)w.numel();
-  TORCH_CHECK(D % 8 == 0 && D <= 16384 && x.numel() % D == 0);
-  const long long R = x.numel() / D;
+// res given: fused residual add, s = bf16(x + res), y = ln(s)·w + b
+static std::vector<at::Tensor> layernorm_fwd_impl(
+    const at::Tensor& x, const c10::optional<at::Tensor>& res,
+    const at::Tensor& w, const at::Tensor& b, double eps) {
+  const auto [R, D] = check_norm_args(x, w, {res});
+  CHECK_BF16_CONTIG(b);
+  TORCH_CHECK(b.numel() == D && b.device() == x.device());
   auto y = at::empty_like(x);
   auto mean = at::empty({R}, x.options().dtype(at::kFloat));
   auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
+  at::Tensor sum_out = res.has_value() ? at::empty_like(x) : at::Tensor();
   acco_layernorm_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(),
-                     mean.data_ptr(), rstd.data_ptr(), nullptr, nullptr, R,
-                     D, (float)eps, cur_stream());
+                     mean.data_ptr(), rstd.data_ptr(), ptr_or_null(res),
+                     res.has_value() ? sum_out.data_ptr() : nullptr, R, D,
+                     (float)eps, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  if (res.has_value()) return {y, sum_out, mean, rstd};
   return {y, mean, rstd};
 }
 
-// fused residual add + LayerNorm: s = bf16(x + res), y = ln(s)·w + b
+std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
+                                      double eps) {
+  return layernorm_fwd_impl(x, c10::nullopt, w, b, eps);
+}
+
 std::vector<at::Tensor> add_layernorm_fwd(at::Tensor x, at::Tensor res,
                                           at::Tensor w, at::Tensor b,
                                           double eps) {
-  CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(res);
-  CHECK_BF16_CONTIG(w); CHECK_BF16_CONTIG(b);
-  const int D = (int)w.numel();
-  TORCH_CHECK(D % 8 == 0 && D <= 16384 && x.numel() % D == 0);
-  TORCH_CHECK(res.numel() == x.numel());
-  const long long R = x.numel() / D;
-  auto y = at::empty_like(x);
-  auto sum_out = at::empty_like(x);
-  auto mean = at::empty({R}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty({R}, x.options().dtype(at::kFloat));
-  acco_layernorm_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(),
-                     mean.data_ptr(), rstd.data_ptr(), res.data_ptr(),
-                     sum_out.data_ptr(), R, D, (float)eps, cur_stream());
-  return {y, sum_out, mean, rstd};
+  return layernorm_fwd_impl(x, res, w, b, eps);
 }
 
 std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x,
                                       at::Tensor w, at::Tensor mean,
                                       at::Tensor rstd,
-                                      c10::optional<at::Tensor> dadd_opt) {
-  at::Tensor dadd = dadd_opt.value_or(at::Tensor());
-  CHECK_BF16_CONTIG(dy); CHECK_BF16_CONTIG(x); CHECK_BF16_CONTIG(w);
-  const int D = (int)w.numel();
-  const long long R = x.numel() / D;
+                                      c10::optional<at::Tensor> dadd) {
+  const auto [R, D] = check_norm_args(x, w, {dy, dadd}, {mean, rstd});
   auto dx = at::empty_like(x);
   const int grid = acco_norm_bwd_grid(R, D);
   auto dw_part = at::empty({grid, D}, x.options().dtype(at::kFloat));
   auto db_part = at::empty({grid, D}, x.options().dtype(at::kFloat));
   acco_layernorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
                      mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-                     dw_part.data_ptr(), db_part.data_ptr(),
-                     (dadd.defined() && dadd.numel() > 0) ? dadd.data_ptr() : nullptr, R, D,
-                     cur_stream());
+                     dw_part.data_ptr(), db_part.data_ptr(), ptr_or_null(dadd),
+                     R, D, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   auto dw = at::empty({D}, w.options());
   auto db = at::empty({D}, w.options());
   acco_norm_dw_finalize(dw_part.data_ptr<float>(), db_part.data_ptr<float>(),
                         dw.data_ptr(), db.data_ptr(), grid, D, true,
                         cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dx, dw, db};
 }
 

@@ -10,6 +10,7 @@
 // ignore_index = -100 tokens contribute nothing.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 

@@ -5,6 +5,7 @@
 // backward wrapper.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 

@@ -4,6 +4,7 @@
 // ATen chains of SURVEY.md §2.5 K1/K2 with one kernel per direction.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 

@@ -14,6 +14,7 @@
 // model only if it beats hipBLASLt on the live shapes.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 

@@ -1,0 +1,119 @@
+// Prototypes of every extern "C" launcher of the gfx950 kernels, the one
+// place a launcher's signature is written down. Each .hip file that defines
+// a launcher includes this header, so the compiler checks the definition
+// against the prototype the bindings call through (extern "C" names are not
+// mangled: a drifted declaration would link cleanly and pass garbage).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+extern "C" {
+
+// ---- adamw.hip
+void acco_fused_adamw_launch(void* p, const void* g, void* m, void* v,
+                             void* out, const float* scale_dev, long long n,
+                             bool buf_is_bf16, bool commit, float scale,
+                             float lr, float beta1, float beta2, float eps,
+                             float weight_decay, long long step_plus_1,
+                             hipStream_t stream);
+
+// ---- elementwise.hip
+void acco_swiglu_fwd(const void* g, const void* u, void* out, long long n,
+                     int cols, long long row_stride8, hipStream_t s);
+void acco_swiglu_bwd(const void* dout, const void* g, const void* u, void* dg,
+                     void* du, long long n, int cols, long long row_stride8,
+                     hipStream_t s);
+void acco_gelu_fwd(const void* x, void* out, long long n, hipStream_t s);
+void acco_gelu_bwd(const void* dout, const void* x, void* dx, long long n,
+                   hipStream_t s);
+
+// ---- norms.hip
+void acco_rmsnorm_fwd(const void* x, const void* w, void* y, void* rstd,
+                      const void* res, void* sum_out, long long R, int D,
+                      float eps, hipStream_t s);
+void acco_rmsnorm_bwd(const void* dy, const void* x, const void* w,
+                      const void* rstd, void* dx, void* dw_fp32,
+                      const void* dadd, long long R, int D, hipStream_t s);
+void acco_layernorm_fwd(const void* x, const void* w, const void* b, void* y,
+                        void* mean, void* rstd, const void* res,
+                        void* sum_out, long long R, int D, float eps,
+                        hipStream_t s);
+void acco_layernorm_bwd(const void* dy, const void* x, const void* w,
+                        const void* mean, const void* rstd, void* dx,
+                        void* dw_fp32, void* db_fp32, const void* dadd,
+                        long long R, int D, hipStream_t s);
+int acco_norm_bwd_grid(long long R, int D);
+void acco_norm_dw_finalize(const float* dw_part, const float* db_part,
+                           void* dw, void* db, int P, int D, bool out_bf16,
+                           hipStream_t s);
+void acco_colsum(const void* in, float* out, long long P, int D,
+                 bool in_is_bf16, hipStream_t s);
+
+// ---- rope.hip
+void acco_rope(const void* x, void* y, const float* cos_t, const float* sin_t,
+               long long B, int S, int H, int D, bool bwd,
+               long long row_stride, hipStream_t stream);
+void acco_rope_qk_inplace(void* qkv, const float* cos_t, const float* sin_t,
+                          long long T, int S, int H, int Hkv, int D,
+                          long long W, long long q_off, long long k_off,
+                          hipStream_t stream);
+
+// ---- ce.hip
+void acco_ce_fwd(const void* logits, const long long* labels, float* lse,
+                 float* acc, long long T, int S, int V, float epsilon,
+                 hipStream_t s);
+void acco_ce_bwd(const void* logits, const long long* labels,
+                 const float* lse, void* dlogits, const float* acc,
+                 float dloss, const float* dloss_dev, long long T, int S,
+                 int V, float epsilon, hipStream_t s);
+
+// ---- gemm_nt.hip
+void acco_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K,
+                  hipStream_t stream);
+
+// ---- attention_fwd.hip, attention_fwd32.hip
+void acco_attn_fwd(const void* q, const void* k, const void* v, void* o,
+                   float* lse, int B, int S, int H, int Hkv, int D,
+                   float scale, int window, hipStream_t stream);
+void acco_attn_fwd32(const void* q, const void* k, const void* v, void* o,
+                     float* lse, int B, int S, int H, int Hkv, int D,
+                     float scale, int window, long long q_rs, long long kv_rs,
+                     long long o_rs, hipStream_t stream);
+
+// ---- attention_bwd.hip, attention_bwd32.hip
+void acco_attn_bwd_dq(const void* q, const void* k, const void* v,
+                      const void* dO, const float* lse, const float* delta,
+                      void* dq, int B, int S, int H, int Hkv, int D,
+                      float scale, int window, hipStream_t stream);
+void acco_attn_bwd_dkv(const void* q, const void* k, const void* v,
+                       const void* dO, const float* lse, const float* delta,
+                       void* dk, void* dv, int B, int S, int H, int Hkv,
+                       int D, float scale, int window, hipStream_t stream);
+void acco_attn_bwd32_dq(const void* q, const void* k, const void* v,
+                        const void* dO, const float* lse, const float* delta,
+                        void* dq, int B, int S, int H, int Hkv, int D,
+                        float scale, int window, long long q_rs,
+                        long long kv_rs, long long do_rs, long long dq_rs,
+                        const float* rope_cos, const float* rope_sin,
+                        hipStream_t stream);
+void acco_attn_bwd32_dkv(const void* q, const void* k, const void* v,
+                         const void* dO, const float* lse,
+                         const float* delta, void* dk, void* dv, int B,
+                         int S, int H, int Hkv, int D, float scale,
+                         int window, long long q_rs, long long kv_rs,
+                         long long do_rs, hipStream_t stream);
+
+// ---- delta.hip
+void acco_attn_delta(const void* dO, const void* O, float* delta, long long B,
+                     int S, int H, int D, hipStream_t stream);
+void acco_attn_gqa_reduce(const void* dkq, const void* dvq, void* dqkv,
+                          long long T, int Hkv, int rep, int D, long long W,
+                          long long k_off, long long v_off,
+                          hipStream_t stream);
+void acco_attn_gqa_reduce_rope(const void* dkq, const void* dvq, void* dqkv,
+                               const float* cos_t, const float* sin_t,
+                               long long T, int S, int Hkv, int rep, int D,
+                               long long W, long long k_off, long long v_off,
+                               hipStream_t stream);
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 //           dx2 = dy2*cos - dy1*sin.
 
 #include "common.h"
+#include "kernels.h"
 
 namespace {
 
