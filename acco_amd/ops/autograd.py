@@ -248,19 +248,11 @@ class AttnQKVPackedFn(torch.autograd.Function):
             # group-sum + inverse rotation of dk + bf16 cast in one pass
             ext.attn_gqa_reduce_rope(dkq, dvq, dqkv, cos, sin, Hkv, rep, D,
                                      k_off, v_off)
-        elif hasattr(ext, "attn_gqa_reduce"):
+        else:
             # one pass: group-sum over the rep query heads + bf16 cast +
             # strided write into the packed grad's k|v sections (replaces
             # two dim-3 sums, two casts and two strided copies per layer)
             ext.attn_gqa_reduce(dkq, dvq, dqkv, Hkv, rep, D, k_off, v_off)
-        elif rep > 1:
-            dk = dkq.view(B, S, Hkv, rep, D).sum(3, dtype=torch.float32)
-            dv = dvq.view(B, S, Hkv, rep, D).sum(3, dtype=torch.float32)
-            dqkv[..., k_off:k_off + Hkv * D] = dk.reshape(B, S, Hkv * D).bfloat16()
-            dqkv[..., v_off:v_off + Hkv * D] = dv.reshape(B, S, Hkv * D).bfloat16()
-        else:
-            dqkv[..., k_off:k_off + Hkv * D] = dkq.reshape(B, S, Hkv * D)
-            dqkv[..., v_off:v_off + Hkv * D] = dvq.reshape(B, S, Hkv * D)
         return (dqkv, None, None, None, None, None, None, None, None)
 
 

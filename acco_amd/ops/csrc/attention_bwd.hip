@@ -17,54 +17,12 @@
 // C-layout products feeding the next MFMA's A side (P, dS) take a
 // per-wave LDS round trip.
 
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 
 namespace {
 
-using u16 = unsigned short;
-using short8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int TILE = 64;
-constexpr int PAD = 8;
-constexpr int LST = TILE + PAD;       // 72: transposed-tile & P row stride
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-// stage a [TILE × D] global tile TRANSPOSED into LDS [D][LST]
-// (paired-row ushort2 writes: half the instructions of scalar b16)
-template <int D>
-ACCO_DEV void stage_transposed(const u16* src, long long row_stride,
-                               u16* dst) {
-  const int r2 = (threadIdx.x & 31) * 2;            // tile row pair
-  for (int dg = threadIdx.x >> 5; dg < D / 8; dg += 8) {
-    ushort4 a0 = reinterpret_cast<const ushort4*>(
-        src + (long long)r2 * row_stride + dg * 8)[0];
-    ushort4 a1 = reinterpret_cast<const ushort4*>(
-        src + (long long)r2 * row_stride + dg * 8)[1];
-    ushort4 b0 = reinterpret_cast<const ushort4*>(
-        src + (long long)(r2 + 1) * row_stride + dg * 8)[0];
-    ushort4 b1 = reinterpret_cast<const ushort4*>(
-        src + (long long)(r2 + 1) * row_stride + dg * 8)[1];
-    u16 av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    u16 bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      *reinterpret_cast<ushort2*>(dst + (dg * 8 + i) * LST + r2) =
-          make_ushort2(av[i], bv[i]);
-  }
-}
-
-// stage a [TILE × D] global tile ROW-MAJOR into LDS [TILE][D+8]
-template <int D>
-ACCO_DEV void stage_rowmajor(const u16* src, long long row_stride, u16* dst) {
-  for (int c = threadIdx.x; c < TILE * (D / 8); c += 256) {
-    const int r = c / (D / 8), dc = c % (D / 8);
-    reinterpret_cast<uint4*>(dst + r * (D + 8))[dc] =
-        *reinterpret_cast<const uint4*>(src + (long long)r * row_stride + dc * 8);
-  }
-}
+using namespace attn;
 
 // ------------------------------------------------------------------- dQ
 template <int D, int QW>
@@ -86,10 +44,11 @@ void attn_bwd_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   const int lg = lane >> 4, lc = lane & 15;
 
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
-  u16* kT_lds = smem;                             // [D][LST]
-  u16* k_row = smem + D * LST;                    // [TILE][KROW]
-  u16* v_row = k_row + TILE * KROW;               // [TILE][KROW]
-  u16* ds_lds = v_row + TILE * KROW + wave * 16 * LST;   // per-wave dS^T
+  using L = BwdDqLds<D, 4>;
+  u16* kT_lds = smem + L::k_t;                    // [D][LST]
+  u16* k_row = smem + L::k_row;                   // [TILE][KROW]
+  u16* v_row = smem + L::v_row;                   // [TILE][KROW]
+  u16* ds_lds = smem + L::ds + wave * 16 * LST;   // per-wave dS^T
 
   const long long qs = (long long)H * D, ks = (long long)Hkv * D;
   const int q0 = qt * QT + wave * QW;
@@ -114,24 +73,16 @@ void attn_bwd_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     delta_c[m] = delta[(long long)bh * S + q0 + m * 16 + lc];
   }
 
-  f32x4 acc_dq[M2][DT];
-#pragma unroll
-  for (int m = 0; m < M2; ++m)
-#pragma unroll
-    for (int t = 0; t < DT; ++t) acc_dq[m][t] = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc_dq[M2][DT] = {};
 
-  int j_lo = 0;
-  if (window > 0) {
-    int kv_min = qt * QT - window + 1;
-    if (kv_min > 0) j_lo = kv_min / TILE;
-  }
-  const int j_hi = (qt * QT + QT - 1) / TILE;
+  const int j_lo = kv_tile_lo(qt * QT, window);
+  const int j_hi = kv_tile_hi(qt * QT, QT);
 
   for (int j = j_lo; j <= j_hi; ++j) {
     __syncthreads();
-    stage_transposed<D>(Kb + (long long)(j * TILE) * ks, ks, kT_lds);
-    stage_rowmajor<D>(Kb + (long long)(j * TILE) * ks, ks, k_row);
-    stage_rowmajor<D>(Vb + (long long)(j * TILE) * ks, ks, v_row);
+    stage_transposed<D, 256>(Kb + (long long)(j * TILE) * ks, ks, kT_lds);
+    stage_rowmajor<D, 256>(Kb + (long long)(j * TILE) * ks, ks, k_row);
+    stage_rowmajor<D, 256>(Vb + (long long)(j * TILE) * ks, ks, v_row);
     __syncthreads();
 
 #pragma unroll
@@ -164,10 +115,8 @@ void attn_bwd_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kv_g = j * TILE + m16 * 16 + lg * 4 + r;
-          bool valid = (kv_g <= q_g);
-          if (window > 0) valid = valid && (kv_g > q_g - window);
-          const float pval =
-              valid ? __expf(st[m16][r] * scale - lse_c[m]) : 0.0f;
+          const float pval = attends(kv_g, q_g, window)
+              ? __expf(st[m16][r] * scale - lse_c[m]) : 0.0f;
           const float dsv = pval * (dpt[m16][r] - delta_c[m]) * scale;
           pk[r] = f32_to_bf16(dsv);
         }
@@ -223,12 +172,15 @@ void attn_bwd_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   const int lg = lane >> 4, lc = lane & 15;
 
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
-  u16* qT_lds = smem;                               // [D][LST]
-  u16* doT_lds = smem + D * LST;                    // [D][LST]
-  u16* q_row = doT_lds + D * LST;                   // [TILE][KROW]
-  u16* do_row = q_row + TILE * KROW;                // [TILE][KROW]
-  u16* p_lds = do_row + TILE * KROW + wave * 16 * LST;
-  u16* ds_lds = do_row + TILE * KROW + (4 + wave) * 16 * LST;
+  using L = BwdDkvLds<D, 4>;
+  u16* qT_lds = smem + L::q_t;                      // [D][LST]
+  u16* doT_lds = smem + L::do_t;                    // [D][LST]
+  u16* q_row = smem + L::q_row;                     // [TILE][KROW]
+  u16* do_row = smem + L::do_row;                   // [TILE][KROW]
+  u16* p_lds = smem + L::p + wave * 16 * LST;       // per-wave P^T
+  // dS^T tiles follow the 4 P^T tiles ((4 + wave) * tile, not a second base
+  // + wave * tile: the latter compiles to different address code)
+  u16* ds_lds = smem + L::p + (4 + wave) * 16 * LST;   // per-wave dS^T
 
   const long long qs = (long long)H * D, ks = (long long)Hkv * D;
   const int kv0 = jb * KB + wave * QW;              // wave's QW kv rows
@@ -249,28 +201,17 @@ void attn_bwd_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
           Vp + (long long)(m * 16 + lc) * ks + s * 32 + lg * 8);
     }
 
-  f32x4 acc_dk[M2][DT], acc_dv[M2][DT];
-#pragma unroll
-  for (int m = 0; m < M2; ++m)
-#pragma unroll
-    for (int t = 0; t < DT; ++t) {
-      acc_dk[m][t] = {0.f, 0.f, 0.f, 0.f};
-      acc_dv[m][t] = {0.f, 0.f, 0.f, 0.f};
-    }
+  f32x4 acc_dk[M2][DT] = {}, acc_dv[M2][DT] = {};
 
-  int qt_hi = S / TILE - 1;
-  if (window > 0) {
-    const int q_lim = jb * KB + KB - 1 + window;
-    qt_hi = min(qt_hi, q_lim / TILE);
-  }
-  const int qt_lo = (jb * KB) / TILE;
+  const int qt_lo = q_tile_lo(jb * KB);
+  const int qt_hi = q_tile_hi(jb * KB, KB, S, window);
 
   for (int qt = qt_lo; qt <= qt_hi; ++qt) {
     __syncthreads();
-    stage_transposed<D>(Qb + (long long)(qt * TILE) * qs, qs, qT_lds);
-    stage_transposed<D>(dOb + (long long)(qt * TILE) * qs, qs, doT_lds);
-    stage_rowmajor<D>(Qb + (long long)(qt * TILE) * qs, qs, q_row);
-    stage_rowmajor<D>(dOb + (long long)(qt * TILE) * qs, qs, do_row);
+    stage_transposed<D, 256>(Qb + (long long)(qt * TILE) * qs, qs, qT_lds);
+    stage_transposed<D, 256>(dOb + (long long)(qt * TILE) * qs, qs, doT_lds);
+    stage_rowmajor<D, 256>(Qb + (long long)(qt * TILE) * qs, qs, q_row);
+    stage_rowmajor<D, 256>(dOb + (long long)(qt * TILE) * qs, qs, do_row);
     __syncthreads();
 
 #pragma unroll
@@ -302,8 +243,7 @@ void attn_bwd_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int q_g = qt * TILE + m16 * 16 + lg * 4 + r;
-          bool valid = (kv_g <= q_g) && (q_g < S);
-          if (window > 0) valid = valid && (kv_g > q_g - window);
+          const bool valid = (q_g < S) && attends(kv_g, q_g, window);
           const float lse_q = lse[(long long)bh * S + min(q_g, S - 1)];
           const float del_q = delta[(long long)bh * S + min(q_g, S - 1)];
           const float pval = valid ? __expf(st[m16][r] * scale - lse_q) : 0.0f;
@@ -365,18 +305,20 @@ void acco_attn_bwd_dq(const void* q, const void* k, const void* v,
                       const void* dO, const float* lse, const float* delta,
                       void* dq, int B, int S, int H, int Hkv, int D,
                       float scale, int window, hipStream_t stream) {
-  if ((D == 64 || D == 128) && S % 256 == 0) {
+  if (use_mfma32(S, D)) {
     acco_attn_bwd32_dq(q, k, v, dO, lse, delta, dq, B, S, H, Hkv, D, scale,
                        window, (long long)H * D, (long long)Hkv * D,
                        (long long)H * D, (long long)H * D, nullptr, nullptr,
                        stream);
     return;
   }
-  const bool wide = (S % 128 == 0) && (D == 64);
-  dim3 grid(S / (wide ? 128 : 64), B * H);
-  const int lds = (D * LST + 2 * TILE * (D + 8) + 4 * 16 * LST) * sizeof(u16);
-#define LQ(DD, QQ) hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, QQ>), grid,     dim3(256), lds, stream, (const u16*)q, (const u16*)k, (const u16*)v,     (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv, scale, window)
-  if (D == 64) { if (wide) LQ(64, 32); else LQ(64, 16); }
+  const bool w = wide(S, D);
+  dim3 grid(S / (w ? 128 : 64), B * H);
+#define LQ(DD, QQ) hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, QQ>), grid, \
+    dim3(256), (BwdDqLds<DD, 4>::bytes), stream, (const u16*)q, \
+    (const u16*)k, (const u16*)v, (const u16*)dO, lse, delta, (u16*)dq, S, H, \
+    Hkv, scale, window)
+  if (D == 64) { if (w) LQ(64, 32); else LQ(64, 16); }
   else         LQ(128, 16);
 #undef LQ
 }
@@ -385,18 +327,19 @@ void acco_attn_bwd_dkv(const void* q, const void* k, const void* v,
                        const void* dO, const float* lse, const float* delta,
                        void* dk, void* dv, int B, int S, int H, int Hkv,
                        int D, float scale, int window, hipStream_t stream) {
-  if ((D == 64 || D == 128) && S % 256 == 0) {
+  if (use_mfma32(S, D)) {
     acco_attn_bwd32_dkv(q, k, v, dO, lse, delta, dk, dv, B, S, H, Hkv, D,
                         scale, window, (long long)H * D, (long long)Hkv * D,
                         (long long)H * D, stream);
     return;
   }
-  const bool wide = (S % 128 == 0) && (D == 64);
-  dim3 grid(S / (wide ? 128 : 64), B * H);
-  const int lds =
-      (2 * D * LST + 2 * TILE * (D + 8) + 8 * 16 * LST) * sizeof(u16);
-#define LK(DD, QQ) hipLaunchKernelGGL((attn_bwd_dkv_kernel<DD, QQ>), grid,     dim3(256), lds, stream, (const u16*)q, (const u16*)k, (const u16*)v,     (const u16*)dO, lse, delta, (u16*)dk, (u16*)dv, S, H, Hkv, scale, window)
-  if (D == 64) { if (wide) LK(64, 32); else LK(64, 16); }
+  const bool w = wide(S, D);
+  dim3 grid(S / (w ? 128 : 64), B * H);
+#define LK(DD, QQ) hipLaunchKernelGGL((attn_bwd_dkv_kernel<DD, QQ>), grid, \
+    dim3(256), (BwdDkvLds<DD, 4>::bytes), stream, (const u16*)q, \
+    (const u16*)k, (const u16*)v, (const u16*)dO, lse, delta, (u16*)dk, \
+    (u16*)dv, S, H, Hkv, scale, window)
+  if (D == 64) { if (w) LK(64, 32); else LK(64, 16); }
   else         LK(128, 16);
 #undef LK
 }

@@ -12,104 +12,12 @@
 //               per 64-q tile S = Q·K^T, dP = dO·V^T (C col = kv),
 //               dV += P^T·dO and dK += dS^T·Q via the same redistribution.
 
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 
 namespace {
 
-using u16 = unsigned short;
-using short8 = __attribute__((ext_vector_type(8))) short;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int KT = 64;            // staged tile rows (kv in dq, q in dkv)
-constexpr int PAD = 8;
-constexpr int LST = KT + PAD;     // 72
-constexpr int QW = 32;            // rows per wave
-constexpr int NW = 8;
-constexpr int BT = QW * NW;       // 256 rows per workgroup
-
-#define MFMA32(a, b, c) \
-  __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-ACCO_DEV unsigned pack_bf16_(float lo, float hi) {
-  // v_cvt_pk_bf16_f32 (RNE, no builtin on gfx950 — guide T12): one
-  // instruction replaces ~9 VALU of manual round-to-nearest-even
-  // bit-twiddling per packed dword. The trailing s_nop 1 covers the
-  // VALU-write → v_permlane32_swap hazard window for the consumer
-  // (guide T21 hazard note; hipcc pads nothing inside asm).
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1"
-      : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// C-layout floats (16 regs of one 32-row sub-tile) → A-fragment for K-step
-// kk (16 of the 32 C rows): su_j = pack(c[8kk+2j], c[8kk+2j+1]) carries row
-// pairs {2hi, 2hi+1, 4+2hi, 5+2hi}; swapping su0↔su2 and su1↔su3 across
-// half-waves yields dword j = row pair 4hi+j (derivation in
-// attention_fwd32.hip).
-ACCO_DEV short8 c_to_afrag(const float* c, int kk) {
-  const float* pp = c + kk * 8;
-  unsigned su0 = pack_bf16_(pp[0], pp[1]);
-  unsigned su1 = pack_bf16_(pp[2], pp[3]);
-  unsigned su2 = pack_bf16_(pp[4], pp[5]);
-  unsigned su3 = pack_bf16_(pp[6], pp[7]);
-  auto r02 = __builtin_amdgcn_permlane32_swap(su0, su2, false, false);
-  auto r13 = __builtin_amdgcn_permlane32_swap(su1, su3, false, false);
-  short8 pa;
-  reinterpret_cast<unsigned*>(&pa)[0] = r02[0];
-  reinterpret_cast<unsigned*>(&pa)[1] = r13[0];
-  reinterpret_cast<unsigned*>(&pa)[2] = r02[1];
-  reinterpret_cast<unsigned*>(&pa)[3] = r13[1];
-  return pa;
-}
-
-// same redistribution over an f32x16 C fragment kept in vector registers
-// (constant kk from an unrolled loop — element reads stay in VGPRs)
-ACCO_DEV short8 c_to_afrag_v(const f32x16& c, int kk) {
-  const int b = kk * 8;
-  unsigned su0 = pack_bf16_(c[b + 0], c[b + 1]);
-  unsigned su1 = pack_bf16_(c[b + 2], c[b + 3]);
-  unsigned su2 = pack_bf16_(c[b + 4], c[b + 5]);
-  unsigned su3 = pack_bf16_(c[b + 6], c[b + 7]);
-  auto r02 = __builtin_amdgcn_permlane32_swap(su0, su2, false, false);
-  auto r13 = __builtin_amdgcn_permlane32_swap(su1, su3, false, false);
-  short8 pa;
-  reinterpret_cast<unsigned*>(&pa)[0] = r02[0];
-  reinterpret_cast<unsigned*>(&pa)[1] = r13[0];
-  reinterpret_cast<unsigned*>(&pa)[2] = r02[1];
-  reinterpret_cast<unsigned*>(&pa)[3] = r13[1];
-  return pa;
-}
-
-// stage a [KT × D] tile TRANSPOSED into [D][LST] (as attention_bwd.hip,
-// 512-thread block version)
-template <int D>
-ACCO_DEV void stage_T(const u16* src, long long stride, u16* dst) {
-  const int r2 = (threadIdx.x & 31) * 2;
-  for (int dg = threadIdx.x >> 5; dg < D / 8; dg += 16) {
-    ushort4 a0 = reinterpret_cast<const ushort4*>(src + (long long)r2 * stride + dg * 8)[0];
-    ushort4 a1 = reinterpret_cast<const ushort4*>(src + (long long)r2 * stride + dg * 8)[1];
-    ushort4 b0 = reinterpret_cast<const ushort4*>(src + (long long)(r2 + 1) * stride + dg * 8)[0];
-    ushort4 b1 = reinterpret_cast<const ushort4*>(src + (long long)(r2 + 1) * stride + dg * 8)[1];
-    u16 av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-    u16 bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      *reinterpret_cast<ushort2*>(dst + (dg * 8 + i) * LST + r2) =
-          make_ushort2(av[i], bv[i]);
-  }
-}
-
-// stage a [KT × D] tile ROW-MAJOR into [KT][D+8] (512-thread block)
-template <int D>
-ACCO_DEV void stage_R(const u16* src, long long stride, u16* dst) {
-  for (int c = threadIdx.x; c < KT * (D / 8); c += 512) {
-    const int r = c / (D / 8), dc = c % (D / 8);
-    reinterpret_cast<uint4*>(dst + r * (D + 8))[dc] =
-        *reinterpret_cast<const uint4*>(src + (long long)r * stride + dc * 8);
-  }
-}
+using namespace attn;
 
 // ------------------------------------------------------------------- dQ
 // D=64 capped at 128 VGPR: 2 co-resident 8-wave blocks per CU, matching
@@ -135,12 +43,13 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   const int lq = lane & 31, hi = lane >> 5;
 
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
-  u16* k_row = smem;                       // [KT][KROW]
-  u16* v_row = k_row + KT * KROW;          // [KT][KROW]
-  u16* kT_lds = v_row + KT * KROW;         // [D][LST]
+  using L = Bwd32DqLds<D>;
+  u16* k_row = smem + L::k_row;            // [TILE][KROW]
+  u16* v_row = smem + L::v_row;            // [TILE][KROW]
+  u16* kT_lds = smem + L::k_t;             // [D][LST]
 
   const long long qs = q_rs, ks = kv_rs;
-  const int q0 = qt * BT + wave * QW;
+  const int q0 = qt * BT32 + wave * QW32;
   const u16* Qp = q + ((long long)b * S + q0) * qs + (long long)h * D;
   const u16* dOp = dO + ((long long)b * S + q0) * do_rs + (long long)h * D;
   const u16* Kb = k + (long long)b * S * ks + (long long)hkv * D;
@@ -160,33 +69,23 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   const float delta_s = delta[(long long)bh * S + q0 + lq] * scale;
   const float scale2 = scale * 1.4426950408889634f;
 
-  f32x16 acc_dq[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc_dq[t][r] = 0.0f;
+  f32x16 acc_dq[DT] = {};
 
-  int j_lo = 0;
-  if (window > 0) {
-    int kv_min = qt * BT - window + 1;
-    if (kv_min > 0) j_lo = kv_min / KT;
-  }
-  const int j_hi = (qt * BT + BT - 1) / KT;
-  const int q_wave_max = q0 + QW - 1;
+  const int j_lo = kv_tile_lo(qt * BT32, window);
+  const int j_hi = kv_tile_hi(qt * BT32, BT32);
+  const int q_wave_max = q0 + QW32 - 1;
 
   for (int j = j_lo; j <= j_hi; ++j) {
     __syncthreads();
-    stage_R<D>(Kb + (long long)(j * KT) * ks, ks, k_row);
-    stage_R<D>(Vb + (long long)(j * KT) * ks, ks, v_row);
-    stage_T<D>(Kb + (long long)(j * KT) * ks, ks, kT_lds);
+    stage_rowmajor<D, 512>(Kb + (long long)(j * TILE) * ks, ks, k_row);
+    stage_rowmajor<D, 512>(Vb + (long long)(j * TILE) * ks, ks, v_row);
+    stage_transposed<D, 512>(Kb + (long long)(j * TILE) * ks, ks, kT_lds);
     __syncthreads();
-    if (j * KT > q_wave_max) continue;
+    if (j * TILE > q_wave_max) continue;
 
 #pragma unroll
     for (int m32 = 0; m32 < 2; ++m32) {
-      f32x16 st, dpt;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { st[r] = 0.0f; dpt[r] = 0.0f; }
+      f32x16 st = {}, dpt = {};
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
@@ -202,18 +101,15 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       // dS^T (C: col=q=lq, row=kv spread); interior tiles (all kv ≤ all q,
       // all within the window) skip the per-element mask predicates
       const int q_g = q0 + lq;
-      const bool need_mask = (j * KT + KT - 1 > q0) ||
-                             (window > 0 && j * KT <= q_wave_max - window);
+      const bool need_mask = (j * TILE + TILE - 1 > q0) ||
+                             (window > 0 && j * TILE <= q_wave_max - window);
       float ds16[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float x = st[r] * scale2 - lse2_c;
         if (need_mask) {
-          const int kv_g =
-              j * KT + m32 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          bool valid = (kv_g <= q_g);
-          if (window > 0) valid = valid && (kv_g > q_g - window);
-          x = valid ? x : -1e30f;
+          const int kv_g = j * TILE + m32 * 32 + c32_row(r, hi);
+          x = attends(kv_g, q_g, window) ? x : -1e30f;
         }
         const float pval = __builtin_amdgcn_exp2f(x);
         ds16[r] = pval * __builtin_fmaf(dpt[r], scale, -delta_s);
@@ -245,7 +141,7 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   if (rope_cos != nullptr) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const int qrow = c32_row(r, hi);
       const float* cr = rope_cos + (long long)(q0 + qrow) * D + lq;
       const float* sr = rope_sin + (long long)(q0 + qrow) * D + lq;
 #pragma unroll
@@ -262,7 +158,7 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int qrow = (r & 3) + 8 * (r >> 2) + 4 * hi;
+    const int qrow = c32_row(r, hi);
 #pragma unroll
     for (int t = 0; t < DT; ++t)
       dQp[(long long)qrow * dq_rs + t * 32 + lq] = f32_to_bf16(acc_dq[t][r]);
@@ -289,14 +185,15 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   const int lq = lane & 31, hi = lane >> 5;
 
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
-  u16* q_row = smem;                        // [KT][KROW]
-  u16* do_row = q_row + KT * KROW;          // [KT][KROW]
-  u16* qT_lds = do_row + KT * KROW;         // [D][LST]
-  u16* doT_lds = qT_lds + D * LST;          // [D][LST]
+  using L = Bwd32DkvLds<D>;
+  u16* q_row = smem + L::q_row;             // [TILE][KROW]
+  u16* do_row = smem + L::do_row;           // [TILE][KROW]
+  u16* qT_lds = smem + L::q_t;              // [D][LST]
+  u16* doT_lds = smem + L::do_t;            // [D][LST]
 
   const long long qs = q_rs, ks = kv_rs;
   const long long od = (long long)H * D;   // dk/dv temps: contiguous [B,S,H,D]
-  const int kv0 = jb * BT + wave * QW;
+  const int kv0 = jb * BT32 + wave * QW32;
   const u16* Kp = k + ((long long)b * S + kv0) * ks + (long long)hkv * D;
   const u16* Vp = v + ((long long)b * S + kv0) * ks + (long long)hkv * D;
   const u16* Qb = q + (long long)b * S * qs + (long long)h * D;
@@ -318,24 +215,16 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     }
   }
 
-  f32x16 acc_dk[DT], acc_dv[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc_dk[t][r] = 0.f; acc_dv[t][r] = 0.f; }
+  f32x16 acc_dk[DT] = {}, acc_dv[DT] = {};
 
-  int qt_hi = S / KT - 1;
-  if (window > 0) {
-    const int q_lim = jb * BT + BT - 1 + window;
-    qt_hi = min(qt_hi, q_lim / KT);
-  }
-  const int qt_lo = (jb * BT) / KT;
+  const int qt_lo = q_tile_lo(jb * BT32);
+  const int qt_hi = q_tile_hi(jb * BT32, BT32, S, window);
   const int kv_wave_min = kv0;
 
   // T14 async staging: hold the next q tile's Q/dO loads in registers
   // across the barrier; the loads stay in flight under the MFMA work.
-  // Transpose staging uses the (d-pair, kv-oct) item scheme of the
-  // forward's V staging: 8 coalesced uint row loads → two ds_write_b128
+  // Transpose staging uses a (d-pair, kv-oct) item scheme of its own:
+  // 8 coalesced uint row loads → two ds_write_b128
   // (replaces 8 narrow ushort2 writes per tensor — 2.4× fewer LDS write
   // cycles). Threads < half stage Q^T, the other half dO^T.
   const bool t_q = (threadIdx.x < 256);   // D=64 only: 256 items per tensor
@@ -343,14 +232,14 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   const int t_d0 = (t_id % 32) * 2;
   const int t_kv8 = (t_id / 32) * 8;
   unsigned streg[8];
-  // row-major staging piece: one uint4 per thread per tensor (KT*D/8/512)
-  static_assert(KT * (D / 8) % 512 == 0, "rowmajor chunks");
-  constexpr int RCH = KT * (D / 8) / 512;
+  // row-major staging piece: one uint4 per thread per tensor (TILE*D/8/512)
+  static_assert(TILE * (D / 8) % 512 == 0, "rowmajor chunks");
+  constexpr int RCH = TILE * (D / 8) / 512;
   uint4 rq[RCH], rdo[RCH];
 
   auto load_qtile = [&](int qt) {
-    const u16* Qs = Qb + (long long)(qt * KT) * qs;
-    const u16* Ds = dOb + (long long)(qt * KT) * do_rs;
+    const u16* Qs = Qb + (long long)(qt * TILE) * qs;
+    const u16* Ds = dOb + (long long)(qt * TILE) * do_rs;
     if (D == 64) {
       // half the threads stage Q^T items, half dO^T items
       const u16* Ts = t_q ? Qs : Ds;
@@ -396,19 +285,12 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   // cross-barrier register staging holds 32 VGPRs for the whole loop and
   // tips the 128-VGPR accumulator build into spilling
   auto stage_qtile_direct = [&](int qt) {
-    const u16* Qs = Qb + (long long)(qt * KT) * qs;
-    const u16* Ds = dOb + (long long)(qt * KT) * do_rs;
-    stage_T<D>(Qs, qs, qT_lds);
-    stage_T<D>(Ds, do_rs, doT_lds);
-#pragma unroll
-    for (int c = 0; c < RCH; ++c) {
-      const int cc = threadIdx.x + c * 512;
-      const int r = cc / (D / 8), dc = cc % (D / 8);
-      reinterpret_cast<uint4*>(q_row + r * KROW)[dc] =
-          *reinterpret_cast<const uint4*>(Qs + (long long)r * qs + dc * 8);
-      reinterpret_cast<uint4*>(do_row + r * KROW)[dc] =
-          *reinterpret_cast<const uint4*>(Ds + (long long)r * do_rs + dc * 8);
-    }
+    const u16* Qs = Qb + (long long)(qt * TILE) * qs;
+    const u16* Ds = dOb + (long long)(qt * TILE) * do_rs;
+    stage_transposed<D, 512>(Qs, qs, qT_lds);
+    stage_transposed<D, 512>(Ds, do_rs, doT_lds);
+    stage_rowmajor<D, 512>(Qs, qs, q_row);
+    stage_rowmajor<D, 512>(Ds, do_rs, do_row);
   };
 
   if constexpr (KV_RES) load_qtile(qt_lo);
@@ -423,20 +305,18 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     if constexpr (KV_RES)
       if (qt < qt_hi) load_qtile(qt + 1);  // in flight under the MFMAs
     // tile fully before this wave's kv rows → all masked: skip compute
-    if (qt * KT + KT - 1 < kv_wave_min) continue;
+    if (qt * TILE + TILE - 1 < kv_wave_min) continue;
 
 #pragma unroll
     for (int m32 = 0; m32 < 2; ++m32) {
-      // per-lane lse/delta for q = qt*KT + m32*32 + lq (broadcast by row),
+      // per-lane lse/delta for q = qt*TILE + m32*32 + lq (broadcast by row),
       // pre-scaled: lse → log2 domain, delta → ·scale (fma fold below)
       const float lse_l =
-          lse[(long long)bh * S + qt * KT + m32 * 32 + lq] * 1.4426950408889634f;
+          lse[(long long)bh * S + qt * TILE + m32 * 32 + lq] * 1.4426950408889634f;
       const float del_l =
-          delta[(long long)bh * S + qt * KT + m32 * 32 + lq] * scale;
+          delta[(long long)bh * S + qt * TILE + m32 * 32 + lq] * scale;
 
-      f32x16 st, dpt;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { st[r] = 0.0f; dpt[r] = 0.0f; }
+      f32x16 st = {}, dpt = {};
       __builtin_amdgcn_s_setprio(1);
       if constexpr (KV_RES) {
 #pragma unroll
@@ -474,21 +354,19 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       const int kv_g = kv0 + lq;
       const float scale2_ = scale * 1.4426950408889634f;
       // interior q tiles (all q ≥ all kv of this wave, all within window)
-      // skip the per-element mask predicates; (q_g < S) holds by S % KT == 0
+      // skip the per-element mask predicates; (q_g < S) holds by S % TILE == 0
       const bool need_mask =
-          (qt * KT < kv0 + QW - 1) ||
-          (window > 0 && kv0 + window <= qt * KT + KT - 1);
+          (qt * TILE < kv0 + QW32 - 1) ||
+          (window > 0 && kv0 + window <= qt * TILE + TILE - 1);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int rr = c32_row(r, hi);
         const float lse_q = __shfl(lse_l, rr, 64);
         const float del_q = __shfl(del_l, rr, 64);
         float x = st[r] * scale2_ - lse_q;
         if (need_mask) {
-          const int q_g = qt * KT + m32 * 32 + rr;
-          bool valid = (kv_g <= q_g);
-          if (window > 0) valid = valid && (kv_g > q_g - window);
-          x = valid ? x : -1e30f;
+          const int q_g = qt * TILE + m32 * 32 + rr;
+          x = attends(kv_g, q_g, window) ? x : -1e30f;
         }
         const float pval = __builtin_amdgcn_exp2f(x);
         st[r] = pval;
@@ -499,8 +377,8 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        short8 pa = c_to_afrag_v(st, kk);
-        short8 dsa = c_to_afrag_v(dpt, kk);
+        short8 pa = c_to_afrag(st, kk);
+        short8 dsa = c_to_afrag(dpt, kk);
         // NOTE: must stay fully unrolled — t indexes the accumulator
         // register arrays (guide rule 20: runtime indexing demotes them
         // to scratch; a partial-unroll experiment cost 576 B/lane)
@@ -522,7 +400,7 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   u16* dVp = dv + ((long long)b * S + kv0) * od + (long long)h * D;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int krow = (r & 3) + 8 * (r >> 2) + 4 * hi;
+    const int krow = c32_row(r, hi);
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
       dKp[(long long)krow * od + t * 32 + lq] = f32_to_bf16(acc_dk[t][r]);
@@ -542,20 +420,13 @@ void acco_attn_bwd32_dq(const void* q, const void* k, const void* v,
                         long long kv_rs, long long do_rs, long long dq_rs,
                         const float* rope_cos, const float* rope_sin,
                         hipStream_t stream) {
-  dim3 grid(S / BT, B * H);
-  const int lds = (2 * KT * (D + 8) + D * LST) * sizeof(u16);
-  if (D == 64)
-    hipLaunchKernelGGL(attn_bwd32_dq_kernel<64>, grid, dim3(512), lds, stream,
-                       (const u16*)q, (const u16*)k, (const u16*)v,
-                       (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv,
-                       scale, window, q_rs, kv_rs, do_rs, dq_rs, rope_cos,
-                       rope_sin);
-  else
-    hipLaunchKernelGGL(attn_bwd32_dq_kernel<128>, grid, dim3(512), lds,
-                       stream, (const u16*)q, (const u16*)k, (const u16*)v,
-                       (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv,
-                       scale, window, q_rs, kv_rs, do_rs, dq_rs, rope_cos,
-                       rope_sin);
+  dim3 grid(S / BT32, B * H);
+#define LQ(DD) hipLaunchKernelGGL(attn_bwd32_dq_kernel<DD>, grid, dim3(512), \
+    Bwd32DqLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
+    (const u16*)v, (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv, scale, \
+    window, q_rs, kv_rs, do_rs, dq_rs, rope_cos, rope_sin)
+  if (D == 64) LQ(64); else LQ(128);
+#undef LQ
 }
 
 void acco_attn_bwd32_dkv(const void* q, const void* k, const void* v,
@@ -564,18 +435,13 @@ void acco_attn_bwd32_dkv(const void* q, const void* k, const void* v,
                          int S, int H, int Hkv, int D, float scale,
                          int window, long long q_rs, long long kv_rs,
                          long long do_rs, hipStream_t stream) {
-  dim3 grid(S / BT, B * H);
-  const int lds = (2 * KT * (D + 8) + 2 * D * LST) * sizeof(u16);
-  if (D == 64)
-    hipLaunchKernelGGL(attn_bwd32_dkv_kernel<64>, grid, dim3(512), lds,
-                       stream, (const u16*)q, (const u16*)k, (const u16*)v,
-                       (const u16*)dO, lse, delta, (u16*)dk, (u16*)dv, S, H,
-                       Hkv, scale, window, q_rs, kv_rs, do_rs);
-  else
-    hipLaunchKernelGGL(attn_bwd32_dkv_kernel<128>, grid, dim3(512), lds,
-                       stream, (const u16*)q, (const u16*)k, (const u16*)v,
-                       (const u16*)dO, lse, delta, (u16*)dk, (u16*)dv, S, H,
-                       Hkv, scale, window, q_rs, kv_rs, do_rs);
+  dim3 grid(S / BT32, B * H);
+#define LK(DD) hipLaunchKernelGGL(attn_bwd32_dkv_kernel<DD>, grid, dim3(512), \
+    Bwd32DkvLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
+    (const u16*)v, (const u16*)dO, lse, delta, (u16*)dk, (u16*)dv, S, H, Hkv, \
+    scale, window, q_rs, kv_rs, do_rs)
+  if (D == 64) LK(64); else LK(128);
+#undef LK
 }
 
 }  // extern "C"

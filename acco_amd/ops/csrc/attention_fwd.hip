@@ -18,20 +18,12 @@
 // - P redistributed q-col→A-fragment layout through a per-wave LDS tile;
 // - causal + optional local window (GPT-Neo 256) + GQA; saves lse.
 
-#include "common.h"
+#include "attention_common.h"
 #include "kernels.h"
 
 namespace {
 
-using u16 = unsigned short;
-using short8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int KT = 64;           // kv rows per tile
-constexpr int VPAD = 8;
-constexpr int LSTRIDE = KT + VPAD;   // 72
-
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+using namespace attn;
 
 template <int D, int QW>         // QW = q rows per wave (16 or 32)
 __global__ __launch_bounds__(256)
@@ -53,10 +45,11 @@ void attn_fwd_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   const int lg = lane >> 4;
   const int lc = lane & 15;
 
+  using L = FwdLds<D, 4>;
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
-  u16* v_lds = smem;                                   // [D][LSTRIDE]
-  u16* k_lds = smem + D * LSTRIDE;                     // [KT][KROW]
-  u16* p_lds = k_lds + KT * KROW + wave * 16 * LSTRIDE;  // per wave [16][LSTRIDE]
+  u16* v_lds = smem + L::v_t;                          // [D][LST]
+  u16* k_lds = smem + L::k_row;                        // [TILE][KROW]
+  u16* p_lds = smem + L::p + wave * 16 * LST;          // per wave [16][LST]
 
   const int q0 = qt * QT + wave * QW;
   const long long qs = (long long)H * D;
@@ -74,55 +67,22 @@ void attn_fwd_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       qf[m][s] = *reinterpret_cast<const short8*>(
           Qp + (long long)(m * 16 + lc) * qs + s * 32 + lg * 8);
 
-  float m_c[M2], l_c[M2];
-  f32x4 acc_o[M2][DT];
+  float m_c[M2], l_c[M2] = {};
+  f32x4 acc_o[M2][DT] = {};
 #pragma unroll
-  for (int m = 0; m < M2; ++m) {
-    m_c[m] = -1e30f;
-    l_c[m] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < DT; ++t) acc_o[m][t] = {0.f, 0.f, 0.f, 0.f};
-  }
+  for (int m = 0; m < M2; ++m) m_c[m] = -1e30f;
 
-  int j_lo = 0;
-  if (window > 0) {
-    int kv_min = qt * QT - window + 1;
-    if (kv_min > 0) j_lo = kv_min / KT;
-  }
-  const int j_hi = (qt * QT + QT - 1) / KT;            // causal
+  const int j_lo = kv_tile_lo(qt * QT, window);
+  const int j_hi = kv_tile_hi(qt * QT, QT);
 
   for (int j = j_lo; j <= j_hi; ++j) {
     // ---- stage V^T (paired-kv ushort2) and K (vector copy); 4 waves share
     __syncthreads();
-    {
-      const u16* Vt = Vb + (long long)(j * KT) * ks;
-      const int kv2 = (threadIdx.x & 31) * 2;
-      for (int dg = threadIdx.x >> 5; dg < D / 8; dg += 8) {
-        ushort4 a0 = reinterpret_cast<const ushort4*>(
-            Vt + (long long)kv2 * ks + dg * 8)[0];
-        ushort4 a1 = reinterpret_cast<const ushort4*>(
-            Vt + (long long)kv2 * ks + dg * 8)[1];
-        ushort4 b0 = reinterpret_cast<const ushort4*>(
-            Vt + (long long)(kv2 + 1) * ks + dg * 8)[0];
-        ushort4 b1 = reinterpret_cast<const ushort4*>(
-            Vt + (long long)(kv2 + 1) * ks + dg * 8)[1];
-        u16 av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-        u16 bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          *reinterpret_cast<ushort2*>(v_lds + (dg * 8 + i) * LSTRIDE + kv2) =
-              make_ushort2(av[i], bv[i]);
-      }
-      const u16* Kt = Kb + (long long)(j * KT) * ks;
-      for (int c = threadIdx.x; c < KT * (D / 8); c += 256) {
-        const int kv = c / (D / 8), dc = c % (D / 8);
-        reinterpret_cast<uint4*>(k_lds + kv * KROW)[dc] =
-            *reinterpret_cast<const uint4*>(Kt + (long long)kv * ks + dc * 8);
-      }
-    }
+    stage_transposed<D, 256>(Vb + (long long)(j * TILE) * ks, ks, v_lds);
+    stage_rowmajor<D, 256>(Kb + (long long)(j * TILE) * ks, ks, k_lds);
     __syncthreads();
 
-    const bool diag = (j * KT + KT - 1) > (qt * QT);   // any masking possible
+    const bool diag = (j * TILE + TILE - 1) > (qt * QT);   // any masking possible
 
 #pragma unroll
     for (int m = 0; m < M2; ++m) {
@@ -150,12 +110,10 @@ void attn_fwd_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       for (int m16 = 0; m16 < 4; ++m16)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int kv_g = j * KT + m16 * 16 + lg * 4 + r;
+          const int kv_g = j * TILE + m16 * 16 + lg * 4 + r;
           float x = st[m16][r] * scale;
           if (diag || window > 0) {
-            bool valid = (kv_g <= q_g);
-            if (window > 0) valid = valid && (kv_g > q_g - window);
-            x = valid ? x : -1e30f;
+            x = attends(kv_g, q_g, window) ? x : -1e30f;
           }
           p[m16 * 4 + r] = x;
           tmax = fmaxf(tmax, x);
@@ -182,7 +140,7 @@ void attn_fwd_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
         u16 pk[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) pk[r] = f32_to_bf16(p[m16 * 4 + r]);
-        *reinterpret_cast<ushort4*>(p_lds + lc * LSTRIDE + m16 * 16 + lg * 4) =
+        *reinterpret_cast<ushort4*>(p_lds + lc * LST + m16 * 16 + lg * 4) =
             make_ushort4(pk[0], pk[1], pk[2], pk[3]);
       }
 
@@ -203,11 +161,11 @@ void attn_fwd_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         short8 pa = *reinterpret_cast<const short8*>(
-            p_lds + lc * LSTRIDE + s * 32 + lg * 8);
+            p_lds + lc * LST + s * 32 + lg * 8);
 #pragma unroll
         for (int t = 0; t < DT; ++t) {
           short8 vb = *reinterpret_cast<const short8*>(
-              v_lds + (t * 16 + lc) * LSTRIDE + s * 32 + lg * 8);
+              v_lds + (t * 16 + lc) * LST + s * 32 + lg * 8);
           acc_o[m][t] = MFMA(pa, vb, acc_o[m][t]);
         }
       }
@@ -243,23 +201,19 @@ extern "C" void acco_attn_fwd(const void* q, const void* k, const void* v,
                               void* o, float* lse, int B, int S, int H,
                               int Hkv, int D, float scale, int window,
                               hipStream_t stream) {
-  if ((D == 64 || D == 128) && S % 256 == 0) {
+  if (use_mfma32(S, D)) {
     // v4: 32x32 MFMA + in-register softmax (attention_fwd32.hip)
     acco_attn_fwd32(q, k, v, o, lse, B, S, H, Hkv, D, scale, window,
                     (long long)H * D, (long long)Hkv * D, (long long)H * D,
                     stream);
     return;
   }
-  const int lds_bytes =
-      (D * LSTRIDE + KT * (D + 8) + 4 * 16 * LSTRIDE) * sizeof(u16);
-  // D=128 at QW=32 needs ~197 VGPR -> 1 wave/SIMD; keep QW=16 there
-  const bool wide = (S % 128 == 0) && (D == 64);
-  const int qt_rows = wide ? 128 : 64;
-  dim3 grid(S / qt_rows, B * H);
+  const bool w = wide(S, D);
+  dim3 grid(S / (w ? 128 : 64), B * H);
 #define LA(DD, QQ) hipLaunchKernelGGL((attn_fwd_kernel<DD, QQ>), grid, \
-    dim3(256), lds_bytes, stream, (const u16*)q, (const u16*)k, \
+    dim3(256), (FwdLds<DD, 4>::bytes), stream, (const u16*)q, (const u16*)k, \
     (const u16*)v, (u16*)o, lse, S, H, Hkv, scale, window)
-  if (D == 64) { if (wide) LA(64, 32); else LA(64, 16); }
+  if (D == 64) { if (w) LA(64, 32); else LA(64, 16); }
   else         LA(128, 16);
 #undef LA
 }

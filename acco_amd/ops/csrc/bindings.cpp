@@ -349,31 +349,93 @@ at::Tensor ce_bwd_dev(at::Tensor logits, at::Tensor labels, at::Tensor lse,
   return dlogits;
 }
 
-// ---- flash attention ([B, S, H, D] layout, D in {64, 128}, S % 64 == 0)
+// ---- flash attention ([B, S, H, D] layout)
+struct AttnShape { int B, S, H, Hkv, D; };
+
+// What every attention kernel needs of its sizes: D in {64, 128}, GQA groups
+// of whole heads, whole tiles (s_mult = 64, or 256 where only the 32x32
+// kernels are launched), window >= 0 and a grid.y that fits.
+static AttnShape check_attn_dims(int64_t B, int64_t S, int64_t H, int64_t Hkv,
+                                 int64_t D, int64_t window, int64_t s_mult) {
+  TORCH_CHECK((D == 64 || D == 128) && H > 0 && Hkv > 0 && H % Hkv == 0,
+              "need D in {64, 128} and H % Hkv == 0, got D=", D, " H=", H,
+              " Hkv=", Hkv);
+  TORCH_CHECK(S > 0 && S % s_mult == 0 && S < (1LL << 30) && window >= 0,
+              "need S % ", s_mult, " == 0 and window >= 0, got S=", S,
+              " window=", window);
+  TORCH_CHECK(B > 0 && B * H <= 65535, "need 1 <= B*H <= 65535 (grid.y), got ",
+              "B=", B, " H=", H);
+  return {(int)B, (int)S, (int)H, (int)Hkv, (int)D};
+}
+
+// every tensor of `same` is contiguous bf16 on ref's device with ref's sizes
+static void check_attn_like(const at::Tensor& ref, const char* what,
+                            std::initializer_list<at::Tensor> same) {
+  for (const at::Tensor& t : same) {
+    CHECK_BF16_CONTIG(t);
+    TORCH_CHECK(t.device() == ref.device() && t.sizes() == ref.sizes(), what,
+                ": expected ", ref.sizes(), " on ", ref.device(), ", got ",
+                t.sizes(), " on ", t.device());
+  }
+}
+
+// lse / delta: contiguous fp32 with one element per (b, h, s)
+static void check_attn_stats(const at::Tensor& ref, const AttnShape& a,
+                             std::initializer_list<at::Tensor> stats) {
+  const int64_t n = (int64_t)a.B * a.H * a.S;
+  for (const at::Tensor& st : stats)
+    TORCH_CHECK(st.is_cuda() && st.device() == ref.device() &&
+                st.scalar_type() == at::kFloat && st.is_contiguous() &&
+                st.numel() == n, "lse/delta must be contiguous CUDA fp32 with "
+                "B*H*S = ", n, " elements, got ", st.numel(), " of ",
+                st.scalar_type());
+}
+
+// The argument contract of the unpacked entry points: q [B,S,H,D] and
+// k, v [B,S,Hkv,D] contiguous bf16 on q's device; each of `like_q` (dO) of
+// q's shape; `stats` (lse, delta) as above.
+static AttnShape check_attn_args(
+    const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+    int64_t window, std::initializer_list<at::Tensor> like_q = {},
+    std::initializer_list<at::Tensor> stats = {}) {
+  CHECK_BF16_CONTIG(q); CHECK_BF16_CONTIG(k);
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && k.device() == q.device() &&
+              k.size(0) == q.size(0) && k.size(1) == q.size(1) &&
+              k.size(3) == q.size(3),
+              "need q [B,S,H,D] and k [B,S,Hkv,D] on one device, got ",
+              q.sizes(), " on ", q.device(), " and ", k.sizes(), " on ",
+              k.device());
+  const AttnShape a = check_attn_dims(q.size(0), q.size(1), q.size(2),
+                                      k.size(2), q.size(3), window, 64);
+  check_attn_like(k, "v against k", {v});
+  check_attn_like(q, "dO against q", like_q);
+  check_attn_stats(q, a, stats);
+  return a;
+}
+
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  double scale, int64_t window) {
-  CHECK_BF16_CONTIG(q); CHECK_BF16_CONTIG(k); CHECK_BF16_CONTIG(v);
-  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4);
-  const int B = (int)q.size(0), S = (int)q.size(1), H = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(2);
-  TORCH_CHECK(S % 64 == 0 && (D == 64 || D == 128) && H % Hkv == 0);
+  const auto [B, S, H, Hkv, D] = check_attn_args(q, k, v, window);
   auto o = at::empty_like(q);
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   acco_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                 lse.data_ptr<float>(), B, S, H, Hkv, D, (float)scale,
                 (int)window, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {o, lse};
 }
 
 at::Tensor attn_delta(at::Tensor dO, at::Tensor o) {
-  CHECK_BF16_CONTIG(dO); CHECK_BF16_CONTIG(o);
+  CHECK_BF16_CONTIG(dO);
+  TORCH_CHECK(dO.dim() == 4 && dO.size(3) % 8 == 0 && dO.size(1) < (1LL << 31),
+              "dO must be [B,S,H,D] with D % 8 == 0, got ", dO.sizes());
+  check_attn_like(dO, "o against dO", {o});
   const long long B = dO.size(0);
   const int S = (int)dO.size(1), H = (int)dO.size(2), D = (int)dO.size(3);
-  TORCH_CHECK(D % 8 == 0);
   auto delta = at::empty({B, H, S}, dO.options().dtype(at::kFloat));
   acco_attn_delta(dO.data_ptr(), o.data_ptr(), delta.data_ptr<float>(), B, S,
                   H, D, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return delta;
 }
 
@@ -381,12 +443,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor dO, at::Tensor lse,
                                  at::Tensor delta, double scale,
                                  int64_t window) {
-  CHECK_BF16_CONTIG(q); CHECK_BF16_CONTIG(k); CHECK_BF16_CONTIG(v);
-  CHECK_BF16_CONTIG(dO);
-  const int B = (int)q.size(0), S = (int)q.size(1), H = (int)q.size(2),
-            D = (int)q.size(3);
-  const int Hkv = (int)k.size(2);
-  TORCH_CHECK(delta.scalar_type() == at::kFloat && delta.is_contiguous());
+  const auto [B, S, H, Hkv, D] =
+      check_attn_args(q, k, v, window, {dO}, {lse, delta});
   auto dq = at::empty_like(q);
   // dk/dv are emitted per QUERY head; the Python wrapper group-reduces
   auto dk = at::empty_like(q);
@@ -395,52 +453,89 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                    lse.data_ptr<float>(), delta.data_ptr<float>(),
                    dq.data_ptr(), B, S, H, Hkv, D, (float)scale, (int)window,
                    cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   acco_attn_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), dO.data_ptr(),
                     lse.data_ptr<float>(), delta.data_ptr<float>(),
                     dk.data_ptr(), dv.data_ptr(), B, S, H, Hkv, D,
                     (float)scale, (int)window, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dq, dk, dv};
 }
 
-// GQA group-reduce of per-query-head dK/dV straight into the packed grad
+// ---- packed-QKV layout: qkv [B, S, W] contiguous bf16, each section
+// (q: H*D wide, k and v: Hkv*D wide) at a caller-given column offset, so
+// both packing orders work (Llama q|k|v, GPT-Neo k|v|q).
+struct PackedSection { const char* name; int64_t off, width; };
+
+// qkv is 3-D contiguous bf16; W and every offset are multiples of 8 (the
+// kernels read 16-byte vectors from base + off); every section lies inside
+// W and no two overlap.
+static void check_packed_layout(const at::Tensor& qkv,
+                                std::initializer_list<PackedSection> secs) {
+  CHECK_BF16_CONTIG(qkv);
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) % 8 == 0,
+              "packed qkv must be [B,S,W] with W % 8 == 0, got ", qkv.sizes());
+  const int64_t W = qkv.size(2);
+  for (const PackedSection& s : secs) {
+    TORCH_CHECK(s.off >= 0 && s.off % 8 == 0 && s.width > 0 &&
+                s.off + s.width <= W, s.name, " section [", s.off, ", ",
+                s.off + s.width, ") must start at a multiple of 8 inside W=",
+                W);
+    for (const PackedSection& t : secs)
+      TORCH_CHECK(&s == &t || s.off + s.width <= t.off ||
+                  t.off + t.width <= s.off, s.name, " section [", s.off, ", ",
+                  s.off + s.width, ") overlaps ", t.name, " section [", t.off,
+                  ", ", t.off + t.width, ")");
+  }
+}
+
+// GQA group-reduce of per-query-head dK/dV [B, S, Hkv*rep, D] straight into
+// the k|v sections of the packed grad; cos/sin given: the inverse RoPE of
+// the k grad is folded in (rep >= 1)
+static void gqa_reduce_impl(const at::Tensor& dkq, const at::Tensor& dvq,
+                            const at::Tensor& dqkv, const at::Tensor* cos_t,
+                            const at::Tensor* sin_t, int64_t Hkv, int64_t rep,
+                            int64_t D, int64_t k_off, int64_t v_off) {
+  CHECK_BF16_CONTIG(dkq);
+  TORCH_CHECK(Hkv > 0 && rep > 0 && D > 0 && D % (cos_t ? 16 : 8) == 0 &&
+              dkq.dim() == 4 && dkq.size(2) == Hkv * rep && dkq.size(3) == D,
+              "dkq/dvq must be [B, S, Hkv*rep, D] with D % ", cos_t ? 16 : 8,
+              " == 0, got ", dkq.sizes(), " for Hkv=", Hkv, " rep=", rep,
+              " D=", D);
+  check_attn_like(dkq, "dvq against dkq", {dvq});
+  check_packed_layout(dqkv, {{"k", k_off, Hkv * D}, {"v", v_off, Hkv * D}});
+  TORCH_CHECK(dqkv.device() == dkq.device() && dqkv.size(0) == dkq.size(0) &&
+              dqkv.size(1) == dkq.size(1), "dqkv must be [B,S,W] on dkq's "
+              "device; dkq is ", dkq.sizes(), ", dqkv is ", dqkv.sizes());
+  const long long T = dkq.size(0) * dkq.size(1);
+  const int S = (int)dkq.size(1);
+  const long long W = dqkv.size(2);
+  if (cos_t) {
+    check_rope_table(*cos_t, *sin_t, S, D, dqkv);
+    TORCH_CHECK(T * Hkv * (D / 16) < (1LL << 31));
+    acco_attn_gqa_reduce_rope(dkq.data_ptr(), dvq.data_ptr(), dqkv.data_ptr(),
+                              cos_t->data_ptr<float>(),
+                              sin_t->data_ptr<float>(), T, S, (int)Hkv,
+                              (int)rep, (int)D, W, k_off, v_off, cur_stream());
+  } else {
+    acco_attn_gqa_reduce(dkq.data_ptr(), dvq.data_ptr(), dqkv.data_ptr(), T,
+                         (int)Hkv, (int)rep, (int)D, W, k_off, v_off,
+                         cur_stream());
+  }
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 void attn_gqa_reduce(at::Tensor dkq, at::Tensor dvq, at::Tensor dqkv,
                      int64_t Hkv, int64_t rep, int64_t D, int64_t k_off,
                      int64_t v_off) {
-  CHECK_BF16_CONTIG(dkq); CHECK_BF16_CONTIG(dvq); CHECK_BF16_CONTIG(dqkv);
-  TORCH_CHECK(D % 8 == 0);
-  TORCH_CHECK(dkq.dim() == 4 && dvq.sizes() == dkq.sizes() &&
-              dkq.size(-1) * dkq.size(-2) == Hkv * rep * D,
-              "dkq/dvq must be [B, S, Hkv*rep, D]");
-  const long long T = dkq.size(0) * dkq.size(1);
-  const long long W = dqkv.size(2);
-  acco_attn_gqa_reduce(dkq.data_ptr(), dvq.data_ptr(), dqkv.data_ptr(), T,
-                       (int)Hkv, (int)rep, (int)D, W, k_off, v_off,
-                       cur_stream());
+  gqa_reduce_impl(dkq, dvq, dqkv, nullptr, nullptr, Hkv, rep, D, k_off, v_off);
 }
 
-// same reduce with the inverse RoPE of the k grad folded in (rep >= 1)
 void attn_gqa_reduce_rope(at::Tensor dkq, at::Tensor dvq, at::Tensor dqkv,
                           at::Tensor cos_t, at::Tensor sin_t, int64_t Hkv,
                           int64_t rep, int64_t D, int64_t k_off,
                           int64_t v_off) {
-  CHECK_BF16_CONTIG(dkq); CHECK_BF16_CONTIG(dvq); CHECK_BF16_CONTIG(dqkv);
-  TORCH_CHECK(dkq.dim() == 4 && dvq.sizes() == dkq.sizes() &&
-              dkq.size(-1) * dkq.size(-2) == Hkv * rep * D,
-              "dkq/dvq must be [B, S, Hkv*rep, D]");
-  TORCH_CHECK(dqkv.dim() == 3 && dqkv.size(0) == dkq.size(0) &&
-              dqkv.size(1) == dkq.size(1));
-  const long long T = dkq.size(0) * dkq.size(1);
-  const int S = (int)dkq.size(1);
-  const long long W = dqkv.size(2);
-  TORCH_CHECK(D % 16 == 0 && W % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0 &&
-              k_off >= 0 && v_off >= 0 && k_off + Hkv * D <= W &&
-              v_off + Hkv * D <= W);
-  check_rope_table(cos_t, sin_t, S, D, dqkv);
-  TORCH_CHECK(T * Hkv * (D / 16) < (1LL << 31));
-  acco_attn_gqa_reduce_rope(dkq.data_ptr(), dvq.data_ptr(), dqkv.data_ptr(),
-                            cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
-                            T, S, (int)Hkv, (int)rep, (int)D, W, k_off, v_off,
-                            cur_stream());
+  gqa_reduce_impl(dkq, dvq, dqkv, &cos_t, &sin_t, Hkv, rep, D, k_off, v_off);
 }
 
 // ---- experimental NT GEMM (C = A · B^T, bf16; bench/refcheck only)
@@ -456,7 +551,8 @@ at::Tensor gemm_nt(at::Tensor A, at::Tensor B) {
 
 // ---- packed-QKV attention path (fused projection output consumed and
 // grad produced with ZERO split/cat copies). qkv: [B, S, W] contiguous with
-// W = (H + 2*Hkv)*D, sections in q|k|v order; D=64, S%256==0 (v4 kernels).
+// W >= (H + 2*Hkv)*D, sections at the given offsets (check_packed_layout);
+// D in {64, 128}, S%256==0 (v4 kernels only).
 std::vector<at::Tensor> rope_packed(at::Tensor src, at::Tensor dst,
                                     at::Tensor cos_t, at::Tensor sin_t,
                                     int64_t off, int64_t Hsec, int64_t D,
@@ -477,16 +573,11 @@ std::vector<at::Tensor> rope_packed(at::Tensor src, at::Tensor dst,
 void rope_qk_inplace(at::Tensor qkv, at::Tensor cos_t, at::Tensor sin_t,
                      int64_t H, int64_t Hkv, int64_t D, int64_t q_off,
                      int64_t k_off) {
-  CHECK_BF16_CONTIG(qkv);
-  TORCH_CHECK(qkv.dim() == 3);
+  check_packed_layout(qkv, {{"q", q_off, H * D}, {"k", k_off, Hkv * D}});
+  TORCH_CHECK(D % 16 == 0, "in-place RoPE needs D % 16 == 0, got ", D);
   const long long T = qkv.size(0) * qkv.size(1);
   const int S = (int)qkv.size(1);
   const long long W = qkv.size(2);
-  TORCH_CHECK(D % 16 == 0 && W % 8 == 0 && q_off % 8 == 0 && k_off % 8 == 0 &&
-              q_off >= 0 && k_off >= 0 && q_off + H * D <= W &&
-              k_off + Hkv * D <= W);
-  TORCH_CHECK(q_off + H * D <= k_off || k_off + Hkv * D <= q_off,
-              "q and k sections overlap");
   check_rope_table(cos_t, sin_t, S, D, qkv);
   TORCH_CHECK(T * (H + Hkv) * (D / 16) < (1LL << 31));
   acco_rope_qk_inplace(qkv.data_ptr(), cos_t.data_ptr<float>(),
@@ -494,20 +585,35 @@ void rope_qk_inplace(at::Tensor qkv, at::Tensor cos_t, at::Tensor sin_t,
                        (int)D, W, q_off, k_off, cur_stream());
 }
 
+// The argument contract of the packed entry points: the layout above with
+// all three sections, the sizes the 32x32 kernels take (S % 256 == 0), and
+// each of `like_qkv` (dqkv) of qkv's shape on qkv's device.
+static AttnShape check_attn_packed_args(
+    const at::Tensor& qkv, int64_t H, int64_t Hkv, int64_t D, int64_t window,
+    int64_t q_off, int64_t k_off, int64_t v_off,
+    std::initializer_list<at::Tensor> like_qkv = {}) {
+  check_packed_layout(qkv, {{"q", q_off, H * D}, {"k", k_off, Hkv * D},
+                            {"v", v_off, Hkv * D}});
+  const AttnShape a =
+      check_attn_dims(qkv.size(0), qkv.size(1), H, Hkv, D, window, 256);
+  check_attn_like(qkv, "dqkv against qkv", like_qkv);
+  return a;
+}
+
 std::vector<at::Tensor> attn_fwd_packed(at::Tensor qkv, int64_t H,
                                         int64_t Hkv, int64_t D, double scale,
                                         int64_t window, int64_t q_off,
                                         int64_t k_off, int64_t v_off) {
-  CHECK_BF16_CONTIG(qkv);
-  const int B = (int)qkv.size(0), S = (int)qkv.size(1);
+  const AttnShape a =
+      check_attn_packed_args(qkv, H, Hkv, D, window, q_off, k_off, v_off);
   const long long W = qkv.size(2);
-  TORCH_CHECK(W >= (H + 2 * Hkv) * D && (D == 64 || D == 128) && S % 256 == 0);
   const u16* base = (const u16*)qkv.data_ptr();
-  auto o = at::empty({B, S, H * D}, qkv.options());
-  auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
+  auto o = at::empty({a.B, a.S, H * D}, qkv.options());
+  auto lse = at::empty({a.B, a.H, a.S}, qkv.options().dtype(at::kFloat));
   acco_attn_fwd32(base + q_off, base + k_off, base + v_off, o.data_ptr(),
-                  lse.data_ptr<float>(), B, S, (int)H, (int)Hkv, (int)D,
+                  lse.data_ptr<float>(), a.B, a.S, a.H, a.Hkv, a.D,
                   (float)scale, (int)window, W, W, H * D, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {o, lse};
 }
 
@@ -519,14 +625,22 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
                                         int64_t k_off, int64_t v_off,
                                         c10::optional<at::Tensor> cos_opt,
                                         c10::optional<at::Tensor> sin_opt) {
-  CHECK_BF16_CONTIG(qkv); CHECK_BF16_CONTIG(dO); CHECK_BF16_CONTIG(dqkv);
-  const int B = (int)qkv.size(0), S = (int)qkv.size(1);
+  const AttnShape a = check_attn_packed_args(qkv, H, Hkv, D, window, q_off,
+                                             k_off, v_off, {dqkv});
+  const int B = a.B, S = a.S;
   const long long W = qkv.size(2);
+  CHECK_BF16_CONTIG(dO);
+  TORCH_CHECK(dO.device() == qkv.device() && dO.dim() == 3 &&
+              dO.size(0) == B && dO.size(1) == S && dO.size(2) == H * D,
+              "dO must be [B,S,H*D] = [", B, ", ", S, ", ", H * D,
+              "] on qkv's device, got ", dO.sizes());
+  check_attn_stats(qkv, a, {lse, delta});
   // cos/sin given: the dq kernel applies the inverse RoPE in its epilogue
+  TORCH_CHECK(cos_opt.has_value() == sin_opt.has_value(),
+              "cos and sin must both be given or both be None");
   const float* rc = nullptr;
   const float* rs = nullptr;
-  if (cos_opt.has_value() && cos_opt->defined() && cos_opt->numel() > 0) {
-    TORCH_CHECK(sin_opt.has_value() && sin_opt->defined());
+  if (cos_opt.has_value()) {
     check_rope_table(*cos_opt, *sin_opt, S, D, qkv);
     rc = cos_opt->data_ptr<float>();
     rs = sin_opt->data_ptr<float>();
@@ -541,11 +655,13 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
                      dbase + q_off, B, S, (int)H, (int)Hkv, (int)D,
                      (float)scale, (int)window, W, W, H * D, W, rc, rs,
                      cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   acco_attn_bwd32_dkv(base + q_off, base + k_off, base + v_off,
                       dO.data_ptr(), lse.data_ptr<float>(),
                       delta.data_ptr<float>(), dkq.data_ptr(),
                       dvq.data_ptr(), B, S, (int)H, (int)Hkv, (int)D,
                       (float)scale, (int)window, W, W, H * D, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dkq, dvq};
 }
 

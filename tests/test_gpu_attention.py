@@ -55,7 +55,7 @@ def test_attn_d128():
 
 
 def test_attn_d128_v4_path():
-    # S % 256 == 0 → the 32x32 v4 fwd/dq kernels with the v3 dkv
+    # S % 256 == 0 → the 32x32 v4 fwd/dq/dkv kernels
     run_case(B=1, S=256, H=4, Hkv=2, D=128, seed=7)
 
 
