@@ -38,7 +38,9 @@ void attn_bwd_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   constexpr int KROW = D + 8;
   constexpr int M2 = QW / 16;        // q sub-tiles per wave
   constexpr int QT = 4 * QW;         // q rows per workgroup
-  const int qt = blockIdx.x, bh = blockIdx.y;
+  const BlockPos pos = block_order(
+      blockIdx.x, S / QT, gridDim.x / (S / QT), true);
+  const int qt = pos.row_block, bh = pos.bh;
   const int b = bh / H, h = bh % H, hkv = h / (H / Hkv);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lg = lane >> 4, lc = lane & 15;
@@ -166,7 +168,9 @@ void attn_bwd_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   constexpr int KROW = D + 8;
   constexpr int M2 = QW / 16;       // kv sub-tiles per wave
   constexpr int KB = 4 * QW;        // kv rows per workgroup
-  const int jb = blockIdx.x, bh = blockIdx.y;
+  const BlockPos pos = block_order(
+      blockIdx.x, S / KB, gridDim.x / (S / KB), false);
+  const int jb = pos.row_block, bh = pos.bh;
   const int b = bh / H, h = bh % H, hkv = h / (H / Hkv);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lg = lane >> 4, lc = lane & 15;
@@ -313,7 +317,7 @@ void acco_attn_bwd_dq(const void* q, const void* k, const void* v,
     return;
   }
   const bool w = wide(S, D);
-  dim3 grid(S / (w ? 128 : 64), B * H);
+  dim3 grid(block_order_grid(S / (w ? 128 : 64), B, H));
 #define LQ(DD, QQ) hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, QQ>), grid, \
     dim3(256), (BwdDqLds<DD, 4>::bytes), stream, (const u16*)q, \
     (const u16*)k, (const u16*)v, (const u16*)dO, lse, delta, (u16*)dq, S, H, \
@@ -334,7 +338,7 @@ void acco_attn_bwd_dkv(const void* q, const void* k, const void* v,
     return;
   }
   const bool w = wide(S, D);
-  dim3 grid(S / (w ? 128 : 64), B * H);
+  dim3 grid(block_order_grid(S / (w ? 128 : 64), B, H));
 #define LK(DD, QQ) hipLaunchKernelGGL((attn_bwd_dkv_kernel<DD, QQ>), grid, \
     dim3(256), (BwdDkvLds<DD, 4>::bytes), stream, (const u16*)q, \
     (const u16*)k, (const u16*)v, (const u16*)dO, lse, delta, (u16*)dk, \

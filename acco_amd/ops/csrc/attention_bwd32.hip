@@ -2,7 +2,7 @@
 // in-register P/dS redistribution (no per-wave LDS round trips), mirroring
 // attention_fwd32.hip. D ∈ {64, 128} and S % 256 == 0 (v3 fallback else);
 // the D=128 dkv build trades K/V register residency and T14 staging for
-// accumulator headroom (see KV_RES) — 256 VGPRs, 6 spilled, occupancy 2.
+// accumulator headroom (see KV_RES) — 256 VGPRs, none spilled, occupancy 2.
 //
 //   dq kernel : grid over 256-row Q blocks (8 waves × 32 q rows);
 //               per 64-kv tile recompute S^T = K·Q^T and dP^T = V·dO^T
@@ -11,6 +11,9 @@
 //   dkv kernel: grid over 256-row KV blocks (8 waves × 32 kv rows);
 //               per 64-q tile S = Q·K^T, dP = dO·V^T (C col = kv),
 //               dV += P^T·dO and dK += dS^T·Q via the same redistribution.
+//               The q tile's lse/delta are staged into LDS with the tile
+//               and read back as float4 per four C rows (no cross-lane
+//               shuffles).
 
 #include "attention_common.h"
 #include "kernels.h"
@@ -37,7 +40,9 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   constexpr int KS = D / 16;
   constexpr int DT = D / 32;
   constexpr int KROW = D + 8;
-  const int qt = blockIdx.x, bh = blockIdx.y;
+  const BlockPos pos = block_order(
+      blockIdx.x, S / BT32, gridDim.x / (S / BT32), true);
+  const int qt = pos.row_block, bh = pos.bh;
   const int b = bh / H, h = bh % H, hkv = h / (H / Hkv);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lq = lane & 31, hi = lane >> 5;
@@ -179,7 +184,9 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   constexpr int KS = D / 16;
   constexpr int DT = D / 32;
   constexpr int KROW = D + 8;
-  const int jb = blockIdx.x, bh = blockIdx.y;
+  const BlockPos pos = block_order(
+      blockIdx.x, S / BT32, gridDim.x / (S / BT32), false);
+  const int jb = pos.row_block, bh = pos.bh;
   const int b = bh / H, h = bh % H, hkv = h / (H / Hkv);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lq = lane & 31, hi = lane >> 5;
@@ -190,6 +197,9 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   u16* do_row = smem + L::do_row;           // [TILE][KROW]
   u16* qT_lds = smem + L::q_t;              // [D][LST]
   u16* doT_lds = smem + L::do_t;            // [D][LST]
+  // the q tile's row statistics, pre-scaled for the log2-domain recompute:
+  // [0, TILE) lse·log2e, [TILE, 2·TILE) delta·scale
+  float* stat_lds = reinterpret_cast<float*>(smem + L::stats);
 
   const long long qs = q_rs, ks = kv_rs;
   const long long od = (long long)H * D;   // dk/dv temps: contiguous [B,S,H,D]
@@ -236,10 +246,17 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   static_assert(TILE * (D / 8) % 512 == 0, "rowmajor chunks");
   constexpr int RCH = TILE * (D / 8) / 512;
   uint4 rq[RCH], rdo[RCH];
+  // waves 0 / 1 stage the tile's 64 lse / delta values (one per thread)
+  const bool st_on = (threadIdx.x < 2 * TILE);
+  const float* st_src = (threadIdx.x < TILE ? lse : delta) +
+                        (long long)bh * S + (threadIdx.x & (TILE - 1));
+  const float st_mul = (threadIdx.x < TILE) ? 1.4426950408889634f : scale;
+  float streg_stat = 0.0f;
 
   auto load_qtile = [&](int qt) {
     const u16* Qs = Qb + (long long)(qt * TILE) * qs;
     const u16* Ds = dOb + (long long)(qt * TILE) * do_rs;
+    if (st_on) streg_stat = st_src[qt * TILE];
     if (D == 64) {
       // half the threads stage Q^T items, half dO^T items
       const u16* Ts = t_q ? Qs : Ds;
@@ -258,6 +275,7 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     }
   };
   auto write_qtile = [&]() {
+    if (st_on) stat_lds[threadIdx.x] = streg_stat * st_mul;
     if (D == 64) {
       uint4 lo, hi4;
       lo.x = (streg[0] & 0xffffu) | (streg[1] << 16);
@@ -291,6 +309,7 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     stage_transposed<D, 512>(Ds, do_rs, doT_lds);
     stage_rowmajor<D, 512>(Qs, qs, q_row);
     stage_rowmajor<D, 512>(Ds, do_rs, do_row);
+    if (st_on) stat_lds[threadIdx.x] = st_src[qt * TILE] * st_mul;
   };
 
   if constexpr (KV_RES) load_qtile(qt_lo);
@@ -309,13 +328,6 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 
 #pragma unroll
     for (int m32 = 0; m32 < 2; ++m32) {
-      // per-lane lse/delta for q = qt*TILE + m32*32 + lq (broadcast by row),
-      // pre-scaled: lse → log2 domain, delta → ·scale (fma fold below)
-      const float lse_l =
-          lse[(long long)bh * S + qt * TILE + m32 * 32 + lq] * 1.4426950408889634f;
-      const float del_l =
-          delta[(long long)bh * S + qt * TILE + m32 * 32 + lq] * scale;
-
       f32x16 st = {}, dpt = {};
       __builtin_amdgcn_s_setprio(1);
       if constexpr (KV_RES) {
@@ -358,11 +370,18 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       const bool need_mask =
           (qt * TILE < kv0 + QW32 - 1) ||
           (window > 0 && kv0 + window <= qt * TILE + TILE - 1);
+      // row statistics from LDS: C registers 4g..4g+3 are the consecutive
+      // rows 8g + 4hi + 0..3 (c32_row), one float4 each; a half-wave reads
+      // one address, a conflict-free broadcast
+      const float* lse_r = stat_lds + m32 * 32 + 4 * hi;
+      const float* del_r = lse_r + TILE;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int rr = c32_row(r, hi);
-        const float lse_q = __shfl(lse_l, rr, 64);
-        const float del_q = __shfl(del_l, rr, 64);
+        const float lse_q =
+            (*reinterpret_cast<const f32x4*>(lse_r + 8 * (r >> 2)))[r & 3];
+        const float del_q =
+            (*reinterpret_cast<const f32x4*>(del_r + 8 * (r >> 2)))[r & 3];
         float x = st[r] * scale2_ - lse_q;
         if (need_mask) {
           const int q_g = qt * TILE + m32 * 32 + rr;
@@ -420,7 +439,7 @@ void acco_attn_bwd32_dq(const void* q, const void* k, const void* v,
                         long long kv_rs, long long do_rs, long long dq_rs,
                         const float* rope_cos, const float* rope_sin,
                         hipStream_t stream) {
-  dim3 grid(S / BT32, B * H);
+  dim3 grid(block_order_grid(S / BT32, B, H));
 #define LQ(DD) hipLaunchKernelGGL(attn_bwd32_dq_kernel<DD>, grid, dim3(512), \
     Bwd32DqLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
     (const u16*)v, (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv, scale, \
@@ -435,7 +454,7 @@ void acco_attn_bwd32_dkv(const void* q, const void* k, const void* v,
                          int S, int H, int Hkv, int D, float scale,
                          int window, long long q_rs, long long kv_rs,
                          long long do_rs, hipStream_t stream) {
-  dim3 grid(S / BT32, B * H);
+  dim3 grid(block_order_grid(S / BT32, B, H));
 #define LK(DD) hipLaunchKernelGGL(attn_bwd32_dkv_kernel<DD>, grid, dim3(512), \
     Bwd32DkvLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
     (const u16*)v, (const u16*)dO, lse, delta, (u16*)dk, (u16*)dv, S, H, Hkv, \

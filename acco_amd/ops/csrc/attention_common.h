@@ -2,7 +2,9 @@
 // attention_fwd32.hip, attention_bwd.hip, attention_bwd32.hip): tile
 // constants, LDS staging, the 32x32 C-layout helpers, the causal/window tile
 // ranges, every kernel's LDS layout and the host-side choice of kernel
-// generation. Device-only apart from the two path predicates at the end.
+// generation, and the order in which a grid's workgroups take their (row
+// block, head). Device-only apart from that order and the two path
+// predicates at the end.
 #pragma once
 
 #include "common.h"
@@ -140,6 +142,34 @@ ACCO_DEV bool attends(int kv_g, int q_g, int window) {
   return valid;
 }
 
+// ------------------------------------------------------------ block order
+// Every attention kernel runs on a 1-D grid of n_blk * BH workgroups
+// (n_blk row blocks of q or kv rows, BH = B * H heads) and takes its
+// (row block, head) from this one function. Workgroups are dealt round-robin
+// over the 8 XCDs in linear id order, so ids with the same id % 8 share an
+// XCD, and a grid starts first to last. Causal cost grows with the row block
+// (forward, dq: heavy_last) or shrinks with it (dkv), so:
+//  - the head is the fast dimension: 8 consecutive ids are 8 heads of ONE
+//    row block, i.e. every XCD gets the same work (exactly when BH % 8 == 0,
+//    within one block otherwise);
+//  - levels go heaviest first, so the light blocks fill in the tail.
+// Placement is an observed property used for speed only: no kernel depends
+// on it for its result. (Permuting the heads of a level so that the query
+// heads of one kv group share an XCD was measured too: dq got slower in the
+// training step, see RESULTS.md, so heads stay in plain order.)
+struct BlockPos { int row_block, bh; };
+
+__host__ __device__ __forceinline__ BlockPos block_order(
+    unsigned id, unsigned n_blk, unsigned BH, bool heavy_last) {
+  const unsigned level = id / BH;
+  return {(int)(heavy_last ? n_blk - 1 - level : level),
+          (int)(id - level * BH)};
+}
+
+inline unsigned block_order_grid(int n_blk, int B, int H) {
+  return (unsigned)n_blk * (unsigned)(B * H);
+}
+
 // ------------------------------------------------------------ LDS layouts
 // Offsets in u16 elements and the total in bytes; the kernel carves its
 // dynamic LDS from the offsets, its launcher passes `bytes`.
@@ -177,7 +207,10 @@ template <int D> struct Bwd32DqLds {             // attn_bwd32_dq_kernel
 template <int D> struct Bwd32DkvLds {            // attn_bwd32_dkv_kernel
   static constexpr int q_row = 0, do_row = q_row + r_tile(D),
                        q_t = do_row + r_tile(D), do_t = q_t + t_tile(D),
-                       bytes = (do_t + t_tile(D)) * sizeof(u16);
+                       stats = do_t + t_tile(D),   // float [2][TILE]: the q
+                                                   // tile's lse·log2e, delta·scale
+                       bytes = stats * sizeof(u16) + 2 * TILE * sizeof(float);
+  static_assert(stats * sizeof(u16) % 16 == 0, "stats rows are read as float4");
 };
 
 // ------------------------------------------------- host: choice of kernels

@@ -36,8 +36,9 @@ void attn_fwd_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   constexpr int M2 = QW / 16;    // q sub-tiles per wave
   constexpr int QT = 4 * QW;     // q rows per workgroup
   constexpr int KROW = D + 8;
-  const int qt = blockIdx.x;
-  const int bh = blockIdx.y;
+  const BlockPos pos = block_order(
+      blockIdx.x, S / QT, gridDim.x / (S / QT), true);
+  const int qt = pos.row_block, bh = pos.bh;
   const int b = bh / H, h = bh % H;
   const int hkv = h / (H / Hkv);
   const int wave = threadIdx.x >> 6;
@@ -209,11 +210,23 @@ extern "C" void acco_attn_fwd(const void* q, const void* k, const void* v,
     return;
   }
   const bool w = wide(S, D);
-  dim3 grid(S / (w ? 128 : 64), B * H);
+  dim3 grid(block_order_grid(S / (w ? 128 : 64), B, H));
 #define LA(DD, QQ) hipLaunchKernelGGL((attn_fwd_kernel<DD, QQ>), grid, \
     dim3(256), (FwdLds<DD, 4>::bytes), stream, (const u16*)q, (const u16*)k, \
     (const u16*)v, (u16*)o, lse, S, H, Hkv, scale, window)
   if (D == 64) { if (w) LA(64, 32); else LA(64, 16); }
   else         LA(128, 16);
 #undef LA
+}
+
+// The (row block, head) of every linear block id, in id order, as the
+// kernels compute it: out is a host array of 2 * n_blk * B * H ints.
+extern "C" void acco_attn_block_order(int* out, int n_blk, int B, int H,
+                                      bool heavy_last) {
+  const unsigned n = block_order_grid(n_blk, B, H);
+  for (unsigned id = 0; id < n; ++id) {
+    const BlockPos pos = block_order(id, n_blk, B * H, heavy_last);
+    out[2 * id] = pos.row_block;
+    out[2 * id + 1] = pos.bh;
+  }
 }

@@ -33,8 +33,9 @@ void attn_fwd32_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                        long long q_rs, long long kv_rs, long long o_rs) {
   constexpr int KS = D / 16;       // QK^T K-steps over head dim (16 each)
   constexpr int DT = D / 32;       // 32-wide d tiles of the output
-  const int qt = blockIdx.x;
-  const int bh = blockIdx.y;
+  const BlockPos pos = block_order(
+      blockIdx.x, S / BT32, gridDim.x / (S / BT32), true);
+  const int qt = pos.row_block, bh = pos.bh;
   const int b = bh / H, h = bh % H;
   const int hkv = h / (H / Hkv);
   const int wave = threadIdx.x >> 6;
@@ -200,7 +201,7 @@ extern "C" void acco_attn_fwd32(const void* q, const void* k, const void* v,
                                 int Hkv, int D, float scale, int window,
                                 long long q_rs, long long kv_rs,
                                 long long o_rs, hipStream_t stream) {
-  dim3 grid(S / BT32, B * H);
+  dim3 grid(block_order_grid(S / BT32, B, H));
 #define LA(DD) hipLaunchKernelGGL(attn_fwd32_kernel<DD>, grid, dim3(512), \
     Fwd32Lds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
     (const u16*)v, (u16*)o, lse, S, H, Hkv, scale, window, q_rs, kv_rs, o_rs)

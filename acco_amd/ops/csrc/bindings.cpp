@@ -354,7 +354,7 @@ struct AttnShape { int B, S, H, Hkv, D; };
 
 // What every attention kernel needs of its sizes: D in {64, 128}, GQA groups
 // of whole heads, whole tiles (s_mult = 64, or 256 where only the 32x32
-// kernels are launched), window >= 0 and a grid.y that fits.
+// kernels are launched), window >= 0 and a 1-D grid that fits.
 static AttnShape check_attn_dims(int64_t B, int64_t S, int64_t H, int64_t Hkv,
                                  int64_t D, int64_t window, int64_t s_mult) {
   TORCH_CHECK((D == 64 || D == 128) && H > 0 && Hkv > 0 && H % Hkv == 0,
@@ -363,8 +363,9 @@ static AttnShape check_attn_dims(int64_t B, int64_t S, int64_t H, int64_t Hkv,
   TORCH_CHECK(S > 0 && S % s_mult == 0 && S < (1LL << 30) && window >= 0,
               "need S % ", s_mult, " == 0 and window >= 0, got S=", S,
               " window=", window);
-  TORCH_CHECK(B > 0 && B * H <= 65535, "need 1 <= B*H <= 65535 (grid.y), got ",
-              "B=", B, " H=", H);
+  TORCH_CHECK(B > 0 && B * H <= 65535 && (S / 64) * B * H < (1LL << 31),
+              "need 1 <= B*H <= 65535 and S/64 * B*H < 2^31 (the 1-D grid), "
+              "got B=", B, " H=", H, " S=", S);
   return {(int)B, (int)S, (int)H, (int)Hkv, (int)D};
 }
 
@@ -460,6 +461,21 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                     (float)scale, (int)window, cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dq, dk, dv};
+}
+
+// The kernels' block order on the host: row i of the int32 [n_blk*B*H, 2]
+// result is the (row block, b*H + h) that linear block id i works on;
+// heavy_last = true is the forward / dq order, false the dkv order.
+at::Tensor attn_block_order(int64_t n_blk, int64_t B, int64_t H,
+                            bool heavy_last) {
+  TORCH_CHECK(B > 0 && H > 0 && B * H <= 65535 && n_blk > 0 &&
+              n_blk < (1LL << 31) && n_blk * B * H < (1LL << 31),
+              "need 1 <= B*H <= 65535 and 1 <= n_blk*B*H < 2^31, got n_blk=",
+              n_blk, " B=", B, " H=", H);
+  auto out = at::empty({n_blk * B * H, 2}, at::TensorOptions().dtype(at::kInt));
+  acco_attn_block_order(out.data_ptr<int>(), (int)n_blk, (int)B, (int)H,
+                        heavy_last);
+  return out;
 }
 
 // ---- packed-QKV layout: qkv [B, S, W] contiguous bf16, each section
@@ -699,6 +715,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_delta", &attn_delta);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_block_order", &attn_block_order, py::arg("n_blk"),
+        py::arg("B"), py::arg("H"), py::arg("heavy_last"));
   m.def("attn_gqa_reduce", &attn_gqa_reduce);
   m.def("attn_gqa_reduce_rope", &attn_gqa_reduce_rope);
   m.def("rope_qk_inplace", &rope_qk_inplace);

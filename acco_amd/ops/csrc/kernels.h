@@ -80,6 +80,11 @@ void acco_attn_fwd32(const void* q, const void* k, const void* v, void* o,
                      float scale, int window, long long q_rs, long long kv_rs,
                      long long o_rs, hipStream_t stream);
 
+// host only: attn::block_order for every block id, out[2 * id] = row block,
+// out[2 * id + 1] = b * H + h (for the tests of the order)
+void acco_attn_block_order(int* out, int n_blk, int B, int H,
+                           bool heavy_last);
+
 // ---- attention_bwd.hip, attention_bwd32.hip
 void acco_attn_bwd_dq(const void* q, const void* k, const void* v,
                       const void* dO, const float* lse, const float* delta,
