@@ -20,7 +20,8 @@ from torch.utils.data import DataLoader, Dataset, RandomSampler
 
 from acco_amd.data.packing import (make_tokenize_const_len_fn,
                                    make_tokenize_truncate_fn)
-from acco_amd.data.synthetic import collate_input_ids
+from acco_amd.data.synthetic import (DocMaskCollator, collate_input_ids,
+                                     resolve_doc_mask_eos)
 from acco_amd.engine import arena
 from acco_amd.engine.acco import AccoEngine
 from acco_amd.engine.bootstrap import DistContext, init_distributed
@@ -98,6 +99,12 @@ class DecoupledTrainer:
         self.loss_div = 1.0
 
         # ---- data
+        # train.doc_mask: packed rows carry `doc_start`, attention stays
+        # inside each document. Const-length path only: right padding under
+        # a causal mask (the finetune collator) needs no boundary mask.
+        self.doc_mask_eos = resolve_doc_mask_eos(
+            getattr(args, "doc_mask", False)
+            and getattr(args, "const_len_batch", True), tokenizer, model)
         self._prepare_data(train_dataset, eval_dataset, preprocess_dataset_fn)
         self.train_dataloader = self._make_dataloader(self.train_dataset,
                                                       shuffle=True)
@@ -201,7 +208,8 @@ class DecoupledTrainer:
 
     def _make_dataloader(self, dataset, shuffle: bool) -> DataLoader:
         if getattr(self.args, "const_len_batch", True):
-            collate = collate_input_ids
+            collate = (collate_input_ids if self.doc_mask_eos is None
+                       else DocMaskCollator(self.doc_mask_eos))
         else:
             # finetune path: ragged sequences, right-padded with labels
             # masked at pads (reference DataCollatorForLanguageModeling,
@@ -254,7 +262,11 @@ class DecoupledTrainer:
                 # fused into the CE HIP kernel on GPU (K9)
                 from acco_amd import ops as _ops
                 labels = inputs.get("labels", inputs["input_ids"])
-                logits = self.model(inputs["input_ids"])[0]
+                if "doc_start" in inputs:
+                    logits = self.model(inputs["input_ids"],
+                                        doc_start=inputs["doc_start"])[0]
+                else:
+                    logits = self.model(inputs["input_ids"])[0]
                 loss = _ops.label_smoothed_causal_lm_loss(
                     logits, labels, ls) / self.loss_div
             else:

@@ -20,6 +20,9 @@ class LlamaConfig:
     rope_theta: float = 500000.0
     tie_word_embeddings: bool = True
     initializer_range: float = 0.02
+    # end-of-document token of packed rows; train.doc_mask reads it when
+    # there is no tokenizer to ask
+    eos_token_id: Optional[int] = None
 
     @property
     def head_dim(self) -> int:
@@ -44,6 +47,7 @@ class LlamaConfig:
             rms_norm_eps=hf.rms_norm_eps,
             rope_theta=getattr(hf, "rope_theta", 10000.0),
             tie_word_embeddings=getattr(hf, "tie_word_embeddings", False),
+            eos_token_id=getattr(hf, "eos_token_id", None),
         )
 
 
@@ -61,6 +65,8 @@ class GPTNeoConfig:
     intermediate_size: Optional[int] = None  # None → 4*hidden (HF default)
     tie_word_embeddings: bool = True
     initializer_range: float = 0.02
+    # end-of-document token of packed rows (see LlamaConfig.eos_token_id)
+    eos_token_id: Optional[int] = None
 
     @property
     def head_dim(self) -> int:
@@ -96,4 +102,5 @@ class GPTNeoConfig:
             attention_pattern=list(j.get("attention_layers", ["global", "local"]))[:2]
             or ["global", "local"],
             intermediate_size=j.get("intermediate_size"),
+            eos_token_id=j.get("eos_token_id"),
         )

@@ -36,7 +36,9 @@ class GPTNeoSelfAttention(nn.Module):
         self.out_proj = nn.Linear(d, d, bias=True)
         self._fused_kvq = None    # (w_view, g_view, splits) via models.fuse
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor,
+                doc_start: Optional[torch.Tensor] = None,
+                doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, S, d = x.shape
         H, hd = self.cfg.num_heads, self.cfg.head_dim
         if self._fused_kvq is not None:
@@ -51,8 +53,9 @@ class GPTNeoSelfAttention(nn.Module):
                 from acco_amd.ops.autograd import AttnQKVPackedFn
                 # GPT-Neo packing order k|v|q; no RoPE; no 1/sqrt(d) scale
                 offs = (2 * d, 0, d)
+                doc = () if doc_start is None else (doc_start, doc_end)
                 o = AttnQKVPackedFn.apply(kvq, None, None, H, H, hd, 1.0,
-                                          window, offs)
+                                          window, offs, *doc)
                 return arena_linear(self.out_proj, o)
             k, v, q = torch.split(kvq, splits, dim=-1)
             q = q.contiguous().view(B, S, H, hd)
@@ -63,7 +66,11 @@ class GPTNeoSelfAttention(nn.Module):
             k = self.k_proj(x).view(B, S, H, hd)
             v = self.v_proj(x).view(B, S, H, hd)
         window = self.cfg.window_size if self.attention_type == "local" else None
-        o = ops.causal_attention(q, k, v, scale=1.0, window=window)
+        if doc_start is None:
+            o = ops.causal_attention(q, k, v, scale=1.0, window=window)
+        else:
+            o = ops.causal_attention(q, k, v, scale=1.0, window=window,
+                                     doc_start=doc_start, doc_end=doc_end)
         return arena_linear(self.out_proj, o.reshape(B, S, d))
 
 
@@ -74,8 +81,8 @@ class GPTNeoAttention(nn.Module):
         super().__init__()
         self.attention = GPTNeoSelfAttention(cfg, cfg.layer_attention_type(layer_id))
 
-    def forward(self, x):
-        return self.attention(x)
+    def forward(self, x, doc_start=None, doc_end=None):
+        return self.attention(x, doc_start, doc_end)
 
 
 class GPTNeoMLP(nn.Module):
@@ -96,13 +103,13 @@ class GPTNeoBlock(nn.Module):
         self.ln_2 = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_epsilon)
         self.mlp = GPTNeoMLP(cfg)
 
-    def forward(self, pending, residual):
+    def forward(self, pending, residual, doc_start=None, doc_end=None):
         """(pending, residual) form — every residual add fused into the
         following LayerNorm kernel (see LlamaDecoderLayer); returns the
         un-added MLP output + running residual, ln_f completes the last add."""
         h1, residual = ops.add_layer_norm(pending, residual, self.ln_1.weight,
                                           self.ln_1.bias, self.ln_1.eps)
-        a = self.attn(h1)
+        a = self.attn(h1, doc_start, doc_end)
         h2, residual = ops.add_layer_norm(a, residual, self.ln_2.weight,
                                           self.ln_2.bias, self.ln_2.eps)
         return self.mlp(h2), residual
@@ -119,20 +126,32 @@ class GPTNeoModel(nn.Module):
         # per-layer activation recompute (train.activation_checkpointing)
         self.gradient_checkpointing = False
 
-    def forward(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, input_ids: torch.Tensor,
+                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
         S = input_ids.shape[1]
         pos = torch.arange(S, device=input_ids.device)
-        pending = self.wte(input_ids) + self.wpe(pos)[None]
+        doc = ()
+        if doc_start is None:
+            pending = self.wte(input_ids) + self.wpe(pos)[None]
+        else:
+            # document masking of packed rows: the learned absolute
+            # positions restart with every document, so a document computes
+            # what it would compute alone in a row. The key-side array of
+            # the backward kernel is derived here, once per forward.
+            doc_start = doc_start.to(device=input_ids.device,
+                                     dtype=torch.int32).contiguous()
+            doc = (doc_start, ops.doc_end_from_start(doc_start))
+            pending = self.wte(input_ids) + self.wpe(pos[None] - doc_start)
         residual = None
         if (self.gradient_checkpointing and self.training
                 and torch.is_grad_enabled()):
             from torch.utils.checkpoint import checkpoint
             for block in self.h:
                 pending, residual = checkpoint(block, pending, residual,
-                                               use_reentrant=False)
+                                               *doc, use_reentrant=False)
         else:
             for block in self.h:
-                pending, residual = block(pending, residual)
+                pending, residual = block(pending, residual, *doc)
         y, _ = ops.add_layer_norm(pending, residual, self.ln_f.weight,
                                   self.ln_f.bias, self.ln_f.eps)
         return y
@@ -164,8 +183,13 @@ class GPTNeoForCausalLM(nn.Module):
 
     def forward(self, input_ids: torch.Tensor,
                 labels: Optional[torch.Tensor] = None,
-                attention_mask: Optional[torch.Tensor] = None):
-        hidden = self.transformer(input_ids)
+                attention_mask: Optional[torch.Tensor] = None,
+                doc_start: Optional[torch.Tensor] = None):
+        """`attention_mask` is accepted and unused; `doc_start` (int32
+        [B, S], ops.doc_start_from_eos) keeps attention inside each document
+        of a packed row and restarts the positions per document."""
+        hidden = (self.transformer(input_ids) if doc_start is None
+                  else self.transformer(input_ids, doc_start))
         logits = arena_linear(self.lm_head, hidden)
         if labels is None:
             return (logits,)

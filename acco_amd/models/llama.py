@@ -44,7 +44,9 @@ class LlamaAttention(nn.Module):
         self.o_proj = nn.Linear(cfg.num_heads * hd, d, bias=False)
         self._fused_qkv = None    # (w_view, g_view, splits) via models.fuse
 
-    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                doc_start: Optional[torch.Tensor] = None,
+                doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, S, _ = x.shape
         cfg = self.cfg
         # keep everything in the projections' natural [B, S, H, D] layout:
@@ -62,9 +64,10 @@ class LlamaAttention(nn.Module):
                 offs = (0, cfg.num_heads * hd,
                         (cfg.num_heads + cfg.num_kv_heads) * hd)
                 # rotates qkv's q|k sections in place; returns (o, qkv)
+                doc = () if doc_start is None else (doc_start, doc_end)
                 o, _ = AttnQKVPackedFn.apply(qkv, cos, sin, cfg.num_heads,
                                              cfg.num_kv_heads, hd,
-                                             hd ** -0.5, 0, offs)
+                                             hd ** -0.5, 0, offs, *doc)
                 return arena_linear(self.o_proj, o)
             q, k, v = torch.split(qkv, splits, dim=-1)
             q = q.contiguous().view(B, S, cfg.num_heads, cfg.head_dim)
@@ -75,7 +78,11 @@ class LlamaAttention(nn.Module):
             k = self.k_proj(x).view(B, S, cfg.num_kv_heads, cfg.head_dim)
             v = self.v_proj(x).view(B, S, cfg.num_kv_heads, cfg.head_dim)
         q, k = ops.rope_apply(q, k, cos, sin)
-        o = ops.causal_attention(q, k, v)          # [B, S, H, D]
+        if doc_start is None:
+            o = ops.causal_attention(q, k, v)      # [B, S, H, D]
+        else:
+            o = ops.causal_attention(q, k, v, doc_start=doc_start,
+                                     doc_end=doc_end)
         return arena_linear(self.o_proj, o.reshape(B, S, -1))
 
 
@@ -117,11 +124,12 @@ class LlamaDecoderLayer(nn.Module):
         self.input_layernorm = LlamaRMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         self.post_attention_layernorm = LlamaRMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
-    def forward(self, pending, residual, cos, sin):
+    def forward(self, pending, residual, cos, sin, doc_start=None,
+                doc_end=None):
         n1 = self.input_layernorm
         h1, residual = ops.add_rms_norm(pending, residual, n1.weight,
                                         n1.variance_epsilon)
-        a = self.self_attn(h1, cos, sin)
+        a = self.self_attn(h1, cos, sin, doc_start, doc_end)
         n2 = self.post_attention_layernorm
         h2, residual = ops.add_rms_norm(a, residual, n2.weight,
                                         n2.variance_epsilon)
@@ -153,19 +161,32 @@ class LlamaModel(nn.Module):
             self._rope_cache = {key: hit}   # keep one entry (static shapes)
         return hit
 
-    def forward(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, input_ids: torch.Tensor,
+                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
         pending = self.embed_tokens(input_ids)
         residual = None
         cos, sin = self._cos_sin(input_ids.shape[1], pending.device)
+        # Document masking of packed rows: RoPE positions stay ABSOLUTE.
+        # A rotated q·k depends only on the distance between the two
+        # positions, and attention never leaves a document, so every score is
+        # what the document would compute alone; no per-row tables needed.
+        # The key-side array of the backward kernel is derived here, once per
+        # forward, not per layer.
+        doc = ()
+        if doc_start is not None:
+            doc_start = doc_start.to(device=pending.device,
+                                     dtype=torch.int32).contiguous()
+            doc = (doc_start, ops.doc_end_from_start(doc_start))
         if (self.gradient_checkpointing and self.training
                 and torch.is_grad_enabled()):
             from torch.utils.checkpoint import checkpoint
             for layer in self.layers:
                 pending, residual = checkpoint(layer, pending, residual,
-                                               cos, sin, use_reentrant=False)
+                                               cos, sin, *doc,
+                                               use_reentrant=False)
         else:
             for layer in self.layers:
-                pending, residual = layer(pending, residual, cos, sin)
+                pending, residual = layer(pending, residual, cos, sin, *doc)
         # final norm completes the last residual add in the same kernel
         y, _ = ops.add_rms_norm(pending, residual, self.norm.weight,
                                 self.norm.variance_epsilon)
@@ -195,11 +216,15 @@ class LlamaForCausalLM(nn.Module):
 
     def forward(self, input_ids: torch.Tensor,
                 labels: Optional[torch.Tensor] = None,
-                attention_mask: Optional[torch.Tensor] = None):
+                attention_mask: Optional[torch.Tensor] = None,
+                doc_start: Optional[torch.Tensor] = None):
         """HF-compatible call: returns (loss, logits) when labels given,
         (logits,) otherwise — the trainer indexes outputs[0]
-        (reference trainer_decoupled.py:29-34)."""
-        hidden = self.model(input_ids)
+        (reference trainer_decoupled.py:29-34). `attention_mask` is accepted
+        and unused. `doc_start` (int32 [B, S], ops.doc_start_from_eos) keeps
+        attention inside each document of a packed row."""
+        hidden = (self.model(input_ids) if doc_start is None
+                  else self.model(input_ids, doc_start))
         logits = arena_linear(self.lm_head, hidden)
         if labels is None:
             return (logits,)

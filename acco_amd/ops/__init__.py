@@ -164,18 +164,54 @@ def rope_apply(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor,
     return RoPEFn.apply(q, k, cos, sin)
 
 
+def doc_start_from_eos(input_ids: torch.Tensor,
+                       eos_token_id: int) -> torch.Tensor:
+    """int32 [B, S] document starts of packed rows (torch_ref docstring);
+    plain torch ops on the device of `input_ids`, no host sync."""
+    return torch_ref.doc_start_from_eos(input_ids, eos_token_id)
+
+
+def doc_end_from_start(doc_start: torch.Tensor) -> torch.Tensor:
+    """int32 [B, S] exclusive document ends, the second array the attention
+    backward (dkv) needs; derive it once per batch, not per layer."""
+    return torch_ref.doc_end_from_start(doc_start)
+
+
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                      scale: Optional[float] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
-    if _use_ref(q, "attn_fwd"):
-        return torch_ref.causal_attention(q, k, v, scale=scale, window=window)
+                     window: Optional[int] = None,
+                     doc_start: Optional[torch.Tensor] = None,
+                     doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`doc_start` (int32 [B, S]): document-boundary masking of packed rows.
+    `doc_end` is doc_end_from_start(doc_start) when the caller has it already
+    (the models derive it once per forward); None derives it here."""
+    if doc_start is None:
+        if _use_ref(q, "attn_fwd"):
+            return torch_ref.causal_attention(q, k, v, scale=scale,
+                                              window=window)
+        S, D = q.shape[1], q.shape[3]
+        if S % 64 != 0 or D not in (64, 128) or q.dtype != torch.bfloat16:
+            # shapes outside the flash kernel's contract (rare: tests, odd
+            # eval batches) run the reference math
+            return torch_ref.causal_attention(q, k, v, scale=scale,
+                                              window=window)
+        from acco_amd.ops.autograd import AttentionFn
+        return AttentionFn.apply(q, k, v, scale, window)
     S, D = q.shape[1], q.shape[3]
-    if S % 64 != 0 or D not in (64, 128) or q.dtype != torch.bfloat16:
-        # shapes outside the flash kernel's contract (rare: tests, odd
-        # eval batches) run the reference math
-        return torch_ref.causal_attention(q, k, v, scale=scale, window=window)
+    if (_use_ref(q, "attn_fwd") or S % 256 != 0 or D not in (64, 128)
+            or q.dtype != torch.bfloat16
+            or (scale is not None and not 0 < scale < 1e30)):
+        # document masks exist in the 32x32 kernels only (and those take a
+        # positive scale with them); every other call runs the reference
+        # math with the mask
+        return torch_ref.causal_attention(q, k, v, scale=scale, window=window,
+                                          doc_start=doc_start)
     from acco_amd.ops.autograd import AttentionFn
-    return AttentionFn.apply(q, k, v, scale, window)
+    doc_start = doc_start.to(torch.int32).contiguous()
+    if doc_end is None:
+        doc_end = doc_end_from_start(doc_start)
+    return AttentionFn.apply(q, k, v, scale, window, doc_start,
+                             doc_end.to(torch.int32).contiguous())
 
 
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:

@@ -198,10 +198,14 @@ class AttnQKVPackedFn(torch.autograd.Function):
     projection is never read again) and the inverse rotation of the grad is
     folded into the dq kernel's epilogue and the GQA reduce; the call then
     returns (o, qkv), since a tensor marked dirty has to be an output.
-    Without RoPE (cos is None) it returns o alone."""
+    Without RoPE (cos is None) it returns o alone.
+
+    doc_start / doc_end (int32 [B, S], both or neither): document-boundary
+    masking of packed rows, the DOC builds of the three kernels."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, H, Hkv, D, scale, window, offs):
+    def forward(ctx, qkv, cos, sin, H, Hkv, D, scale, window, offs,
+                doc_start=None, doc_end=None):
         ext = ops.hip_ext()
         qkv = qkv.contiguous()
         q_off, k_off, v_off = offs
@@ -215,11 +219,22 @@ class AttnQKVPackedFn(torch.autograd.Function):
                 ctx.mark_dirty(qkv)
             ext.rope_qk_inplace(qkv, cos, sin, H, Hkv, D, q_off, k_off)
         roped = qkv
-        o, lse = ext.attn_fwd_packed(roped, H, Hkv, D, float(scale),
-                                     int(window or 0), q_off, k_off, v_off)
+        if (doc_start is None) != (doc_end is None):
+            raise RuntimeError("doc_start and doc_end must both be given "
+                               "or both be None")
+        if doc_start is None:
+            o, lse = ext.attn_fwd_packed(roped, H, Hkv, D, float(scale),
+                                         int(window or 0), q_off, k_off,
+                                         v_off)
+        else:
+            o, lse = ext.attn_fwd_packed(roped, H, Hkv, D, float(scale),
+                                         int(window or 0), q_off, k_off,
+                                         v_off, doc_start)
         ctx.save_for_backward(roped, o, lse,
                               cos if cos is not None else torch.empty(0),
-                              sin if sin is not None else torch.empty(0))
+                              sin if sin is not None else torch.empty(0),
+                              *(() if doc_start is None
+                                else (doc_start, doc_end)))
         ctx.meta = (H, Hkv, D, float(scale), int(window or 0), offs)
         if cos is None:
             return o                 # [B, S, H*D]; qkv untouched
@@ -229,7 +244,8 @@ class AttnQKVPackedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dO, _droped=None):
         ext = ops.hip_ext()
-        roped, o, lse, cos, sin = ctx.saved_tensors
+        roped, o, lse, cos, sin, *doc = ctx.saved_tensors
+        doc_start, doc_end = doc if doc else (None, None)
         H, Hkv, D, scale, window, offs = ctx.meta
         q_off, k_off, v_off = offs
         B, S, W = roped.shape
@@ -242,7 +258,8 @@ class AttnQKVPackedFn(torch.autograd.Function):
         dkq, dvq = ext.attn_bwd_packed(roped, dO, lse, delta, dqkv, H, Hkv,
                                        D, scale, window, q_off, k_off, v_off,
                                        cos if rope else None,
-                                       sin if rope else None)
+                                       sin if rope else None,
+                                       doc_start, doc_end)
         rep = H // Hkv
         if rope:
             # group-sum + inverse rotation of dk + bf16 cast in one pass
@@ -253,17 +270,19 @@ class AttnQKVPackedFn(torch.autograd.Function):
             # strided write into the packed grad's k|v sections (replaces
             # two dim-3 sums, two casts and two strided copies per layer)
             ext.attn_gqa_reduce(dkq, dvq, dqkv, Hkv, rep, D, k_off, v_off)
-        return (dqkv, None, None, None, None, None, None, None, None)
+        return (dqkv, None, None, None, None, None, None, None, None,
+                None, None)
 
 
 class AttentionFn(torch.autograd.Function):
     """Flash-style causal attention, gfx950 MFMA (fwd: online softmax;
     bwd: FA2-style recompute, dq + dkv kernels). [B,S,H,D] layout,
     D ∈ {64,128}, S % 64 == 0 (the dispatch falls back to torch_ref for
-    other shapes)."""
+    other shapes). doc_start / doc_end (int32 [B, S], both or neither):
+    document-boundary masking of packed rows; needs S % 256 == 0."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, window):
+    def forward(ctx, q, k, v, scale, window, doc_start=None, doc_end=None):
         import math
         if scale is None:
             scale = 1.0 / math.sqrt(q.shape[-1])
@@ -271,21 +290,31 @@ class AttentionFn(torch.autograd.Function):
         q = q.contiguous()
         k = k.contiguous()
         v = v.contiguous()
-        o, lse = ops.hip_ext().attn_fwd(q, k, v, float(scale), w)
-        ctx.save_for_backward(q, k, v, o, lse)
+        if (doc_start is None) != (doc_end is None):
+            raise RuntimeError("doc_start and doc_end must both be given "
+                               "or both be None")
+        if doc_start is None:
+            o, lse = ops.hip_ext().attn_fwd(q, k, v, float(scale), w)
+            ctx.save_for_backward(q, k, v, o, lse)
+        else:
+            o, lse = ops.hip_ext().attn_fwd(q, k, v, float(scale), w,
+                                            doc_start)
+            ctx.save_for_backward(q, k, v, o, lse, doc_start, doc_end)
         ctx.scale = float(scale)
         ctx.window = w
         return o
 
     @staticmethod
     def backward(ctx, dO):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, *doc = ctx.saved_tensors
+        doc_start, doc_end = doc if doc else (None, None)
         dO = dO.contiguous()
         # Delta[b,h,s] = rowsum(dO ∘ O) in fp32, laid out [B,H,S] (one
         # fused kernel; was a 4-kernel ATen cast/mul/reduce chain)
         delta = ops.hip_ext().attn_delta(dO, o)
         dq, dkq, dvq = ops.hip_ext().attn_bwd(q, k, v, dO, lse, delta,
-                                              ctx.scale, ctx.window)
+                                              ctx.scale, ctx.window,
+                                              doc_start, doc_end)
         B, S, H, D = q.shape
         Hkv = k.shape[2]
         if Hkv != H:
@@ -294,4 +323,4 @@ class AttentionFn(torch.autograd.Function):
             dv = dvq.view(B, S, Hkv, rep, D).sum(3, dtype=torch.float32).to(v.dtype)
         else:
             dk, dv = dkq, dvq
-        return dq, dk, dv, None, None
+        return dq, dk, dv, None, None, None, None

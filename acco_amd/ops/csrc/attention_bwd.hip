@@ -313,7 +313,7 @@ void acco_attn_bwd_dq(const void* q, const void* k, const void* v,
     acco_attn_bwd32_dq(q, k, v, dO, lse, delta, dq, B, S, H, Hkv, D, scale,
                        window, (long long)H * D, (long long)Hkv * D,
                        (long long)H * D, (long long)H * D, nullptr, nullptr,
-                       stream);
+                       nullptr, stream);
     return;
   }
   const bool w = wide(S, D);
@@ -334,7 +334,7 @@ void acco_attn_bwd_dkv(const void* q, const void* k, const void* v,
   if (use_mfma32(S, D)) {
     acco_attn_bwd32_dkv(q, k, v, dO, lse, delta, dk, dv, B, S, H, Hkv, D,
                         scale, window, (long long)H * D, (long long)Hkv * D,
-                        (long long)H * D, stream);
+                        (long long)H * D, nullptr, stream);
     return;
   }
   const bool w = wide(S, D);

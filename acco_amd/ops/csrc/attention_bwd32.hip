@@ -25,7 +25,10 @@ using namespace attn;
 // ------------------------------------------------------------------- dQ
 // D=64 capped at 128 VGPR: 2 co-resident 8-wave blocks per CU, matching
 // the forward kernel's occupancy choice.
-template <int D>
+// DOC (document boundaries, attention_common.h): as in the forward kernel
+// the lane's column is one query, so its doc_start joined with the window
+// is one lower bound per lane. DOC = false compiles to the kernel without it.
+template <int D, bool DOC>
 __global__ __launch_bounds__(512, D == 64 ? 4 : 2)
 void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                           const u16* __restrict__ v, const u16* __restrict__ dO,
@@ -36,7 +39,8 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                           long long q_rs, long long kv_rs, long long do_rs,
                           long long dq_rs,
                           const float* __restrict__ rope_cos,   // [S, D] or
-                          const float* __restrict__ rope_sin) { // null = off
+                          const float* __restrict__ rope_sin,   // null = off
+                          const int* __restrict__ doc_start) {  // [B,S], DOC
   constexpr int KS = D / 16;
   constexpr int DT = D / 32;
   constexpr int KROW = D + 8;
@@ -76,9 +80,20 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 
   f32x16 acc_dq[DT] = {};
 
-  const int j_lo = kv_tile_lo(qt * BT32, window);
+  int j_lo = kv_tile_lo(qt * BT32, window);
   const int j_hi = kv_tile_hi(qt * BT32, BT32);
   const int q_wave_max = q0 + QW32 - 1;
+  // DOC: lo_q = lowest key of the lane's query; ds_w0 / ds_w1 = doc_start of
+  // the wave's first / last row (wave-uniform)
+  int lo_q = 0, ds_w0 = 0, ds_w1 = 0;
+  if constexpr (DOC) {
+    const int* ds = doc_start + (long long)b * S;
+    lo_q = doc_lo(ds[q0 + lq], q0 + lq, window);
+    ds_w0 = __builtin_amdgcn_readfirstlane(ds[q0]);
+    ds_w1 = __builtin_amdgcn_readfirstlane(ds[q_wave_max]);
+    j_lo = kv_tile_lo_doc(qt * BT32, window,
+                          __builtin_amdgcn_readfirstlane(ds[qt * BT32]), S);
+  }
 
   for (int j = j_lo; j <= j_hi; ++j) {
     __syncthreads();
@@ -87,6 +102,8 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     stage_transposed<D, 512>(Kb + (long long)(j * TILE) * ks, ks, kT_lds);
     __syncthreads();
     if (j * TILE > q_wave_max) continue;
+    if constexpr (DOC)      // all kv before the wave's first document
+      if (j * TILE + TILE - 1 < ds_w0) continue;
 
 #pragma unroll
     for (int m32 = 0; m32 < 2; ++m32) {
@@ -106,16 +123,31 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       // dS^T (C: col=q=lq, row=kv spread); interior tiles (all kv ≤ all q,
       // all within the window) skip the per-element mask predicates
       const int q_g = q0 + lq;
-      const bool need_mask = (j * TILE + TILE - 1 > q0) ||
-                             (window > 0 && j * TILE <= q_wave_max - window);
+      bool need_mask = (j * TILE + TILE - 1 > q0) ||
+                       (window > 0 && j * TILE <= q_wave_max - window);
+      if constexpr (DOC) need_mask = need_mask || (j * TILE < ds_w1);
+      // DOC: one wave-uniform branch per sub-tile masks the raw scores in
+      // place with -inf (scale > 0 with document bounds, see the bindings):
+      // exp2 gives the plain kernel's exact zero. The empty volatile asm
+      // keeps it a branch, as in the forward kernel.
+      if constexpr (DOC)
+        if (__builtin_amdgcn_readfirstlane((int)need_mask)) {
+          asm volatile("");
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int kv_g = j * TILE + m32 * 32 + c32_row(r, hi);
+            st[r] = attends_lo(kv_g, q_g, lo_q) ? st[r] : -INFINITY;
+          }
+        }
       float ds16[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float x = st[r] * scale2 - lse2_c;
-        if (need_mask) {
-          const int kv_g = j * TILE + m32 * 32 + c32_row(r, hi);
-          x = attends(kv_g, q_g, window) ? x : -1e30f;
-        }
+        if constexpr (!DOC)
+          if (need_mask) {
+            const int kv_g = j * TILE + m32 * 32 + c32_row(r, hi);
+            x = attends(kv_g, q_g, window) ? x : -1e30f;
+          }
         const float pval = __builtin_amdgcn_exp2f(x);
         ds16[r] = pval * __builtin_fmaf(dpt[r], scale, -delta_s);
       }
@@ -171,7 +203,12 @@ void attn_bwd32_dq_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
 }
 
 // ---------------------------------------------------------------- dK, dV
-template <int D>
+// DOC: the lane's column is one KEY here, so the mask comes from the key's
+// side: q_g < doc_end[b, kv_g], joined with the window into one exclusive
+// upper bound per lane. The block's last row shortens qt_hi (the T14
+// prefetch follows it), the wave's last / first row extend the whole-tile
+// skip and the interior shortcut.
+template <int D, bool DOC>
 __global__ __launch_bounds__(512)
 void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                            const u16* __restrict__ v,
@@ -180,7 +217,8 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                            const float* __restrict__ delta,
                            u16* __restrict__ dk, u16* __restrict__ dv,
                            int S, int H, int Hkv, float scale, int window,
-                           long long q_rs, long long kv_rs, long long do_rs) {
+                           long long q_rs, long long kv_rs, long long do_rs,
+                           const int* __restrict__ doc_end) {  // [B,S], DOC
   constexpr int KS = D / 16;
   constexpr int DT = D / 32;
   constexpr int KROW = D + 8;
@@ -228,8 +266,20 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   f32x16 acc_dk[DT] = {}, acc_dv[DT] = {};
 
   const int qt_lo = q_tile_lo(jb * BT32);
-  const int qt_hi = q_tile_hi(jb * BT32, BT32, S, window);
+  int qt_hi = q_tile_hi(jb * BT32, BT32, S, window);
   const int kv_wave_min = kv0;
+  // DOC: hi_k = exclusive end of the queries of the lane's key; de_w0 /
+  // de_w1 = doc_end of the wave's first / last row (wave-uniform)
+  int hi_k = 0, de_w0 = 0, de_w1 = 0;
+  if constexpr (DOC) {
+    const int* de = doc_end + (long long)b * S;
+    hi_k = doc_hi(de[kv0 + lq], kv0 + lq, window);
+    de_w0 = __builtin_amdgcn_readfirstlane(de[kv0]);
+    de_w1 = __builtin_amdgcn_readfirstlane(de[kv0 + QW32 - 1]);
+    qt_hi = q_tile_hi_doc(
+        jb * BT32, BT32, S, window,
+        __builtin_amdgcn_readfirstlane(de[jb * BT32 + BT32 - 1]));
+  }
 
   // T14 async staging: hold the next q tile's Q/dO loads in registers
   // across the barrier; the loads stay in flight under the MFMA work.
@@ -325,6 +375,8 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       if (qt < qt_hi) load_qtile(qt + 1);  // in flight under the MFMAs
     // tile fully before this wave's kv rows → all masked: skip compute
     if (qt * TILE + TILE - 1 < kv_wave_min) continue;
+    if constexpr (DOC)      // all q after the wave's last document
+      if (qt * TILE >= de_w1) continue;
 
 #pragma unroll
     for (int m32 = 0; m32 < 2; ++m32) {
@@ -367,14 +419,26 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
       const float scale2_ = scale * 1.4426950408889634f;
       // interior q tiles (all q ≥ all kv of this wave, all within window)
       // skip the per-element mask predicates; (q_g < S) holds by S % TILE == 0
-      const bool need_mask =
+      bool need_mask =
           (qt * TILE < kv0 + QW32 - 1) ||
           (window > 0 && kv0 + window <= qt * TILE + TILE - 1);
+      if constexpr (DOC)
+        need_mask = need_mask || (qt * TILE + TILE - 1 >= de_w0);
       // row statistics from LDS: C registers 4g..4g+3 are the consecutive
       // rows 8g + 4hi + 0..3 (c32_row), one float4 each; a half-wave reads
       // one address, a conflict-free broadcast
       const float* lse_r = stat_lds + m32 * 32 + 4 * hi;
       const float* del_r = lse_r + TILE;
+      // DOC: one wave-uniform branch, raw scores masked in place (see dq)
+      if constexpr (DOC)
+        if (__builtin_amdgcn_readfirstlane((int)need_mask)) {
+          asm volatile("");
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int q_g = qt * TILE + m32 * 32 + c32_row(r, hi);
+            st[r] = attends_hi(kv_g, q_g, hi_k) ? st[r] : -INFINITY;
+          }
+        }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int rr = c32_row(r, hi);
@@ -383,10 +447,11 @@ void attn_bwd32_dkv_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
         const float del_q =
             (*reinterpret_cast<const f32x4*>(del_r + 8 * (r >> 2)))[r & 3];
         float x = st[r] * scale2_ - lse_q;
-        if (need_mask) {
-          const int q_g = qt * TILE + m32 * 32 + rr;
-          x = attends(kv_g, q_g, window) ? x : -1e30f;
-        }
+        if constexpr (!DOC)
+          if (need_mask) {
+            const int q_g = qt * TILE + m32 * 32 + rr;
+            x = attends(kv_g, q_g, window) ? x : -1e30f;
+          }
         const float pval = __builtin_amdgcn_exp2f(x);
         st[r] = pval;
         dpt[r] = pval * __builtin_fmaf(dpt[r], scale, -del_q);
@@ -438,13 +503,20 @@ void acco_attn_bwd32_dq(const void* q, const void* k, const void* v,
                         float scale, int window, long long q_rs,
                         long long kv_rs, long long do_rs, long long dq_rs,
                         const float* rope_cos, const float* rope_sin,
-                        hipStream_t stream) {
+                        const int* doc_start, hipStream_t stream) {
   dim3 grid(block_order_grid(S / BT32, B, H));
-#define LQ(DD) hipLaunchKernelGGL(attn_bwd32_dq_kernel<DD>, grid, dim3(512), \
-    Bwd32DqLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
+  // doc_start given: the DOC build; a window >= S bounds nothing, and
+  // capping it keeps doc_lo / doc_hi free of overflow
+#define LQ(DD, DOC) hipLaunchKernelGGL((attn_bwd32_dq_kernel<DD, DOC>), grid, \
+    dim3(512), Bwd32DqLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
     (const u16*)v, (const u16*)dO, lse, delta, (u16*)dq, S, H, Hkv, scale, \
-    window, q_rs, kv_rs, do_rs, dq_rs, rope_cos, rope_sin)
-  if (D == 64) LQ(64); else LQ(128);
+    DOC ? (window < S ? window : S) : window, q_rs, kv_rs, do_rs, dq_rs, \
+    rope_cos, rope_sin, doc_start)
+  if (doc_start != nullptr) {
+    if (D == 64) LQ(64, true); else LQ(128, true);
+  } else {
+    if (D == 64) LQ(64, false); else LQ(128, false);
+  }
 #undef LQ
 }
 
@@ -453,13 +525,19 @@ void acco_attn_bwd32_dkv(const void* q, const void* k, const void* v,
                          const float* delta, void* dk, void* dv, int B,
                          int S, int H, int Hkv, int D, float scale,
                          int window, long long q_rs, long long kv_rs,
-                         long long do_rs, hipStream_t stream) {
+                         long long do_rs, const int* doc_end,
+                         hipStream_t stream) {
   dim3 grid(block_order_grid(S / BT32, B, H));
-#define LK(DD) hipLaunchKernelGGL(attn_bwd32_dkv_kernel<DD>, grid, dim3(512), \
-    Bwd32DkvLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
+#define LK(DD, DOC) hipLaunchKernelGGL((attn_bwd32_dkv_kernel<DD, DOC>), grid, \
+    dim3(512), Bwd32DkvLds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
     (const u16*)v, (const u16*)dO, lse, delta, (u16*)dk, (u16*)dv, S, H, Hkv, \
-    scale, window, q_rs, kv_rs, do_rs)
-  if (D == 64) LK(64); else LK(128);
+    scale, DOC ? (window < S ? window : S) : window, q_rs, kv_rs, do_rs, \
+    doc_end)
+  if (doc_end != nullptr) {
+    if (D == 64) LK(64, true); else LK(128, true);
+  } else {
+    if (D == 64) LK(64, false); else LK(128, false);
+  }
 #undef LK
 }
 

@@ -142,6 +142,46 @@ ACCO_DEV bool attends(int kv_g, int q_g, int window) {
   return valid;
 }
 
+// ------------------------------------------------- document boundaries
+// Packed rows: doc_start[b, s] is the first token of the document that holds
+// token s, doc_end[b, s] the exclusive end of it; both int32 [B, S] and
+// non-decreasing along s. Query i attends key j iff doc_start[i] <= j <= i
+// (and j > i - window), or from the key's side j <= i < doc_end[j]. In the
+// 32x32 kernels a lane's column is ONE query (forward, dq) or ONE key (dkv),
+// so the document and the window bound fold into one int per lane and the
+// mask stays two compares per element. The arrays are data: every tile
+// index derived from them is clamped into [0, S/TILE - 1], so their content
+// can change numbers but never an address.
+ACCO_DEV int clamp_tile(int t, int S) { return max(0, min(t, S / TILE - 1)); }
+
+// lowest key that query q_g attends to (its lane's doc_start value ds_q)
+ACCO_DEV int doc_lo(int ds_q, int q_g, int window) {
+  return window > 0 ? max(ds_q, q_g - window + 1) : ds_q;
+}
+// exclusive upper end of the queries that attend to key kv_g (doc_end de_k)
+ACCO_DEV int doc_hi(int de_k, int kv_g, int window) {
+  return window > 0 ? min(de_k, kv_g + window) : de_k;
+}
+ACCO_DEV bool attends_lo(int kv_g, int q_g, int lo) {
+  return kv_g <= q_g && kv_g >= lo;
+}
+ACCO_DEV bool attends_hi(int kv_g, int q_g, int hi) {
+  return kv_g <= q_g && q_g < hi;
+}
+
+// kv_tile_lo joined with the document of the block's first q row (ds_first =
+// doc_start there; the rows after it start no earlier)
+ACCO_DEV int kv_tile_lo_doc(int q_blk0, int window, int ds_first, int S) {
+  return max(kv_tile_lo(q_blk0, window), clamp_tile(ds_first / TILE, S));
+}
+// q_tile_hi joined with the document of the block's last kv row (de_last =
+// doc_end there; the rows before it end no later)
+ACCO_DEV int q_tile_hi_doc(int kv_blk0, int rows, int S, int window,
+                           int de_last) {
+  return min(q_tile_hi(kv_blk0, rows, S, window),
+             clamp_tile((max(de_last, 1) - 1) / TILE, S));
+}
+
 // ------------------------------------------------------------ block order
 // Every attention kernel runs on a 1-D grid of n_blk * BH workgroups
 // (n_blk row blocks of q or kv rows, BH = B * H heads) and takes its

@@ -206,7 +206,7 @@ extern "C" void acco_attn_fwd(const void* q, const void* k, const void* v,
     // v4: 32x32 MFMA + in-register softmax (attention_fwd32.hip)
     acco_attn_fwd32(q, k, v, o, lse, B, S, H, Hkv, D, scale, window,
                     (long long)H * D, (long long)Hkv * D, (long long)H * D,
-                    stream);
+                    nullptr, stream);
     return;
   }
   const bool w = wide(S, D);

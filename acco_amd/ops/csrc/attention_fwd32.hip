@@ -24,13 +24,20 @@ using namespace attn;
 // D=64 is capped at 128 VGPR: 2 co-resident 8-wave blocks per CU (4
 // waves/SIMD) out-weigh scheduling freedom — measured faster than the
 // uncapped 159-VGPR build and than a 204-VGPR T14 double-buffered variant.
-template <int D>
+//
+// DOC: document-boundary masking for packed rows (attention_common.h). The
+// lane's column is one query, so doc_start[b, q_g] joined with the window is
+// ONE lower bound per lane; the block's first row shortens the tile range,
+// the wave's first / last row extend the whole-tile skip and the interior
+// shortcut. DOC = false compiles to the kernel without any of it.
+template <int D, bool DOC>
 __global__ __launch_bounds__(512, D == 64 ? 4 : 2)
 void attn_fwd32_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
                        const u16* __restrict__ v, u16* __restrict__ o,
                        float* __restrict__ lse,        // [B, H, S]
                        int S, int H, int Hkv, float scale, int window,
-                       long long q_rs, long long kv_rs, long long o_rs) {
+                       long long q_rs, long long kv_rs, long long o_rs,
+                       const int* __restrict__ doc_start) {  // [B, S], DOC
   constexpr int KS = D / 16;       // QK^T K-steps over head dim (16 each)
   constexpr int DT = D / 32;       // 32-wide d tiles of the output
   const BlockPos pos = block_order(
@@ -65,9 +72,20 @@ void attn_fwd32_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   float m_c = -1e30f, l_c = 0.0f;      // per q col = lq (dup over hi)
   f32x16 acc_o[DT] = {};
 
-  const int j_lo = kv_tile_lo(qt * BT32, window);
+  int j_lo = kv_tile_lo(qt * BT32, window);
   const int j_hi = kv_tile_hi(qt * BT32, BT32);
   const int q_wave_max = q0 + QW32 - 1;
+  // DOC: lo_q = lowest key of the lane's query; ds_w0 / ds_w1 = doc_start of
+  // the wave's first / last row (wave-uniform)
+  int lo_q = 0, ds_w0 = 0, ds_w1 = 0;
+  if constexpr (DOC) {
+    const int* ds = doc_start + (long long)b * S;
+    lo_q = doc_lo(ds[q0 + lq], q0 + lq, window);
+    ds_w0 = __builtin_amdgcn_readfirstlane(ds[q0]);
+    ds_w1 = __builtin_amdgcn_readfirstlane(ds[q_wave_max]);
+    j_lo = kv_tile_lo_doc(qt * BT32, window,
+                          __builtin_amdgcn_readfirstlane(ds[qt * BT32]), S);
+  }
   const float scale2 = scale * 1.4426950408889634f;   // log2 domain
   constexpr float THR2 = 8.0f * 1.4426950408889634f;  // defer-max (T13)
 
@@ -83,6 +101,8 @@ void attn_fwd32_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     if (j * TILE > q_wave_max ||
         (window > 0 && j * TILE + TILE - 1 <= q0 - window))
       continue;
+    if constexpr (DOC)      // all kv before the wave's first document
+      if (j * TILE + TILE - 1 < ds_w0) continue;
 
     // ---- S^T: st[m32] per 32-kv sub-tile (C: col=q=lq, row=kv spread)
     f32x16 st[2];
@@ -105,22 +125,54 @@ void attn_fwd32_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
     // WAVE-level mask class: interior tiles (all kv ≤ all q, all in window)
     // skip the per-element predicates entirely.
     const int q_g = q0 + lq;
-    const bool need_mask = (j * TILE + TILE - 1 > q0) ||
-                           (window > 0 && j * TILE <= q_wave_max - window);
+    bool need_mask = (j * TILE + TILE - 1 > q0) ||
+                     (window > 0 && j * TILE <= q_wave_max - window);
+    if constexpr (DOC) need_mask = need_mask || (j * TILE < ds_w1);
     float p[32];
     float tmax = -1e30f;
+    if constexpr (!DOC) {
 #pragma unroll
-    for (int m32 = 0; m32 < 2; ++m32)
+      for (int m32 = 0; m32 < 2; ++m32)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int kv_g = j * TILE + m32 * 32 + c32_row(r, hi);
-        float x = st[m32][r] * scale2;
-        if (need_mask) {
-          x = attends(kv_g, q_g, window) ? x : -1e30f;
+        for (int r = 0; r < 16; ++r) {
+          const int kv_g = j * TILE + m32 * 32 + c32_row(r, hi);
+          float x = st[m32][r] * scale2;
+          if (need_mask) {
+            x = attends(kv_g, q_g, window) ? x : -1e30f;
+          }
+          p[m32 * 16 + r] = x;
+          tmax = fmaxf(tmax, x);
         }
-        p[m32 * 16 + r] = x;
-        tmax = fmaxf(tmax, x);
+    } else {
+      // DOC: ONE wave-uniform branch per tile that masks the raw scores in
+      // place; -inf survives the scaling (the bindings require scale > 0
+      // with document bounds) and the exp2 below yields the same exact zero
+      // as the plain kernel's -1e30. Left inside the element loop, the
+      // two-compare predicate is turned into 32 unconditional selects and
+      // interior tiles pay for them (forward 20% slower than the plain
+      // kernel on one document); the empty volatile asm keeps the compiler
+      // from doing that here too. Masking after the scaling instead costs
+      // the D=64 build 12 B of scratch.
+      if (__builtin_amdgcn_readfirstlane((int)need_mask)) {
+        asm volatile("");
+#pragma unroll
+        for (int m32 = 0; m32 < 2; ++m32)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int kv_g = j * TILE + m32 * 32 + c32_row(r, hi);
+            st[m32][r] =
+                attends_lo(kv_g, q_g, lo_q) ? st[m32][r] : -INFINITY;
+          }
       }
+#pragma unroll
+      for (int m32 = 0; m32 < 2; ++m32)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float x = st[m32][r] * scale2;
+          p[m32 * 16 + r] = x;
+          tmax = fmaxf(tmax, x);
+        }
+    }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
 
     // ---- T13 defer-max: skip the O-rescale pass (16 shfl + 32 mul) while
@@ -200,11 +252,19 @@ extern "C" void acco_attn_fwd32(const void* q, const void* k, const void* v,
                                 void* o, float* lse, int B, int S, int H,
                                 int Hkv, int D, float scale, int window,
                                 long long q_rs, long long kv_rs,
-                                long long o_rs, hipStream_t stream) {
+                                long long o_rs, const int* doc_start,
+                                hipStream_t stream) {
   dim3 grid(block_order_grid(S / BT32, B, H));
-#define LA(DD) hipLaunchKernelGGL(attn_fwd32_kernel<DD>, grid, dim3(512), \
-    Fwd32Lds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
-    (const u16*)v, (u16*)o, lse, S, H, Hkv, scale, window, q_rs, kv_rs, o_rs)
-  if (D == 64) LA(64); else LA(128);
+  // doc_start given: the DOC build; a window >= S bounds nothing, and
+  // capping it keeps doc_lo / doc_hi free of overflow
+#define LA(DD, DOC) hipLaunchKernelGGL((attn_fwd32_kernel<DD, DOC>), grid, \
+    dim3(512), Fwd32Lds<DD>::bytes, stream, (const u16*)q, (const u16*)k, \
+    (const u16*)v, (u16*)o, lse, S, H, Hkv, scale, \
+    DOC ? (window < S ? window : S) : window, q_rs, kv_rs, o_rs, doc_start)
+  if (doc_start != nullptr) {
+    if (D == 64) LA(64, true); else LA(128, true);
+  } else {
+    if (D == 64) LA(64, false); else LA(128, false);
+  }
 #undef LA
 }

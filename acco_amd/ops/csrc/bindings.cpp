@@ -392,6 +392,28 @@ static void check_attn_stats(const at::Tensor& ref, const AttnShape& a,
                 st.scalar_type());
 }
 
+// doc_start / doc_end (document bounds of packed rows): contiguous int32
+// [B, S] on ref's device. The kernels that take them are the 32x32
+// generation only, so S % 256 == 0 is required with them, and a positive
+// scale (the forward kernel masks raw scores with -inf before scaling).
+static const int* check_attn_doc(const at::Tensor& ref, const AttnShape& a,
+                                 const c10::optional<at::Tensor>& doc,
+                                 const char* name, double scale) {
+  if (!doc.has_value()) return nullptr;
+  const at::Tensor& t = *doc;
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device() &&
+              t.scalar_type() == at::kInt && t.is_contiguous() &&
+              t.dim() == 2 && t.size(0) == a.B && t.size(1) == a.S, name,
+              " must be contiguous int32 [B, S] = [", a.B, ", ", a.S,
+              "] on ", ref.device(), ", got ", t.scalar_type(), " ",
+              t.sizes(), " on ", t.device());
+  TORCH_CHECK(a.S % 256 == 0, name, " needs S % 256 == 0 (the 32x32 "
+              "kernels), got S=", a.S);
+  TORCH_CHECK(scale > 0 && scale < 1e30, name, " needs a positive finite "
+              "scale, got ", scale);
+  return t.data_ptr<int>();
+}
+
 // The argument contract of the unpacked entry points: q [B,S,H,D] and
 // k, v [B,S,Hkv,D] contiguous bf16 on q's device; each of `like_q` (dO) of
 // q's shape; `stats` (lse, delta) as above.
@@ -415,13 +437,23 @@ static AttnShape check_attn_args(
 }
 
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 double scale, int64_t window) {
-  const auto [B, S, H, Hkv, D] = check_attn_args(q, k, v, window);
+                                 double scale, int64_t window,
+                                 c10::optional<at::Tensor> doc_start) {
+  const AttnShape a = check_attn_args(q, k, v, window);
+  const auto [B, S, H, Hkv, D] = a;
+  const int* ds = check_attn_doc(q, a, doc_start, "doc_start", scale);
   auto o = at::empty_like(q);
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
-  acco_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                lse.data_ptr<float>(), B, S, H, Hkv, D, (float)scale,
-                (int)window, cur_stream());
+  if (ds != nullptr) {
+    acco_attn_fwd32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                    lse.data_ptr<float>(), B, S, H, Hkv, D, (float)scale,
+                    (int)window, (long long)H * D, (long long)Hkv * D,
+                    (long long)H * D, ds, cur_stream());
+  } else {
+    acco_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                  lse.data_ptr<float>(), B, S, H, Hkv, D, (float)scale,
+                  (int)window, cur_stream());
+  }
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {o, lse};
 }
@@ -443,13 +475,35 @@ at::Tensor attn_delta(at::Tensor dO, at::Tensor o) {
 std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  at::Tensor dO, at::Tensor lse,
                                  at::Tensor delta, double scale,
-                                 int64_t window) {
-  const auto [B, S, H, Hkv, D] =
-      check_attn_args(q, k, v, window, {dO}, {lse, delta});
+                                 int64_t window,
+                                 c10::optional<at::Tensor> doc_start,
+                                 c10::optional<at::Tensor> doc_end) {
+  const AttnShape a = check_attn_args(q, k, v, window, {dO}, {lse, delta});
+  const auto [B, S, H, Hkv, D] = a;
+  TORCH_CHECK(doc_start.has_value() == doc_end.has_value(),
+              "doc_start and doc_end must both be given or both be None");
+  const int* ds = check_attn_doc(q, a, doc_start, "doc_start", scale);
+  const int* de = check_attn_doc(q, a, doc_end, "doc_end", scale);
   auto dq = at::empty_like(q);
   // dk/dv are emitted per QUERY head; the Python wrapper group-reduces
   auto dk = at::empty_like(q);
   auto dv = at::empty_like(q);
+  if (ds != nullptr) {
+    const long long qr = (long long)H * D, kr = (long long)Hkv * D;
+    acco_attn_bwd32_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                       dO.data_ptr(), lse.data_ptr<float>(),
+                       delta.data_ptr<float>(), dq.data_ptr(), B, S, H, Hkv,
+                       D, (float)scale, (int)window, qr, kr, qr, qr, nullptr,
+                       nullptr, ds, cur_stream());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    acco_attn_bwd32_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                        dO.data_ptr(), lse.data_ptr<float>(),
+                        delta.data_ptr<float>(), dk.data_ptr(), dv.data_ptr(),
+                        B, S, H, Hkv, D, (float)scale, (int)window, qr, kr,
+                        qr, de, cur_stream());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    return {dq, dk, dv};
+  }
   acco_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(), dO.data_ptr(),
                    lse.data_ptr<float>(), delta.data_ptr<float>(),
                    dq.data_ptr(), B, S, H, Hkv, D, (float)scale, (int)window,
@@ -619,16 +673,18 @@ static AttnShape check_attn_packed_args(
 std::vector<at::Tensor> attn_fwd_packed(at::Tensor qkv, int64_t H,
                                         int64_t Hkv, int64_t D, double scale,
                                         int64_t window, int64_t q_off,
-                                        int64_t k_off, int64_t v_off) {
+                                        int64_t k_off, int64_t v_off,
+                                        c10::optional<at::Tensor> doc_start) {
   const AttnShape a =
       check_attn_packed_args(qkv, H, Hkv, D, window, q_off, k_off, v_off);
+  const int* ds = check_attn_doc(qkv, a, doc_start, "doc_start", scale);
   const long long W = qkv.size(2);
   const u16* base = (const u16*)qkv.data_ptr();
   auto o = at::empty({a.B, a.S, H * D}, qkv.options());
   auto lse = at::empty({a.B, a.H, a.S}, qkv.options().dtype(at::kFloat));
   acco_attn_fwd32(base + q_off, base + k_off, base + v_off, o.data_ptr(),
                   lse.data_ptr<float>(), a.B, a.S, a.H, a.Hkv, a.D,
-                  (float)scale, (int)window, W, W, H * D, cur_stream());
+                  (float)scale, (int)window, W, W, H * D, ds, cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {o, lse};
 }
@@ -640,9 +696,15 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
                                         int64_t window, int64_t q_off,
                                         int64_t k_off, int64_t v_off,
                                         c10::optional<at::Tensor> cos_opt,
-                                        c10::optional<at::Tensor> sin_opt) {
+                                        c10::optional<at::Tensor> sin_opt,
+                                        c10::optional<at::Tensor> doc_start,
+                                        c10::optional<at::Tensor> doc_end) {
   const AttnShape a = check_attn_packed_args(qkv, H, Hkv, D, window, q_off,
                                              k_off, v_off, {dqkv});
+  TORCH_CHECK(doc_start.has_value() == doc_end.has_value(),
+              "doc_start and doc_end must both be given or both be None");
+  const int* ds = check_attn_doc(qkv, a, doc_start, "doc_start", scale);
+  const int* de = check_attn_doc(qkv, a, doc_end, "doc_end", scale);
   const int B = a.B, S = a.S;
   const long long W = qkv.size(2);
   CHECK_BF16_CONTIG(dO);
@@ -669,14 +731,15 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
   acco_attn_bwd32_dq(base + q_off, base + k_off, base + v_off, dO.data_ptr(),
                      lse.data_ptr<float>(), delta.data_ptr<float>(),
                      dbase + q_off, B, S, (int)H, (int)Hkv, (int)D,
-                     (float)scale, (int)window, W, W, H * D, W, rc, rs,
+                     (float)scale, (int)window, W, W, H * D, W, rc, rs, ds,
                      cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   acco_attn_bwd32_dkv(base + q_off, base + k_off, base + v_off,
                       dO.data_ptr(), lse.data_ptr<float>(),
                       delta.data_ptr<float>(), dkq.data_ptr(),
                       dvq.data_ptr(), B, S, (int)H, (int)Hkv, (int)D,
-                      (float)scale, (int)window, W, W, H * D, cur_stream());
+                      (float)scale, (int)window, W, W, H * D, de,
+                      cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dkq, dvq};
 }
@@ -712,9 +775,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd_dev", &ce_bwd_dev, py::arg("logits"), py::arg("labels"),
         py::arg("lse"), py::arg("acc"), py::arg("dloss_dev"),
         py::arg("epsilon") = 0.0);
-  m.def("attn_fwd", &attn_fwd);
+  m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("scale"), py::arg("window"),
+        py::arg("doc_start") = py::none());
   m.def("attn_delta", &attn_delta);
-  m.def("attn_bwd", &attn_bwd);
+  m.def("attn_bwd", &attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("dO"), py::arg("lse"), py::arg("delta"), py::arg("scale"),
+        py::arg("window"), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("attn_block_order", &attn_block_order, py::arg("n_blk"),
         py::arg("B"), py::arg("H"), py::arg("heavy_last"));
   m.def("attn_gqa_reduce", &attn_gqa_reduce);
@@ -722,11 +790,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_qk_inplace", &rope_qk_inplace);
   m.def("gemm_nt", &gemm_nt);
   m.def("rope_packed", &rope_packed);
-  m.def("attn_fwd_packed", &attn_fwd_packed);
+  m.def("attn_fwd_packed", &attn_fwd_packed, py::arg("qkv"), py::arg("H"),
+        py::arg("Hkv"), py::arg("D"), py::arg("scale"), py::arg("window"),
+        py::arg("q_off"), py::arg("k_off"), py::arg("v_off"),
+        py::arg("doc_start") = py::none());
   m.def("attn_bwd_packed", &attn_bwd_packed, py::arg("qkv"), py::arg("dO"),
         py::arg("lse"), py::arg("delta"), py::arg("dqkv"), py::arg("H"),
         py::arg("Hkv"), py::arg("D"), py::arg("scale"), py::arg("window"),
         py::arg("q_off"), py::arg("k_off"), py::arg("v_off"),
-        py::arg("cos") = py::none(), py::arg("sin") = py::none());
+        py::arg("cos") = py::none(), py::arg("sin") = py::none(),
+        py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
   m.attr("_gfx950") = true;
 }

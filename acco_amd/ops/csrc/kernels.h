@@ -72,13 +72,17 @@ void acco_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K,
                   hipStream_t stream);
 
 // ---- attention_fwd.hip, attention_fwd32.hip
+// The 32x32 launchers take document bounds for packed rows: doc_start (fwd,
+// dq) / doc_end (dkv), int32 [B, S] on the device, or nullptr for the plain
+// causal / window kernels.
 void acco_attn_fwd(const void* q, const void* k, const void* v, void* o,
                    float* lse, int B, int S, int H, int Hkv, int D,
                    float scale, int window, hipStream_t stream);
 void acco_attn_fwd32(const void* q, const void* k, const void* v, void* o,
                      float* lse, int B, int S, int H, int Hkv, int D,
                      float scale, int window, long long q_rs, long long kv_rs,
-                     long long o_rs, hipStream_t stream);
+                     long long o_rs, const int* doc_start,
+                     hipStream_t stream);
 
 // host only: attn::block_order for every block id, out[2 * id] = row block,
 // out[2 * id + 1] = b * H + h (for the tests of the order)
@@ -100,13 +104,14 @@ void acco_attn_bwd32_dq(const void* q, const void* k, const void* v,
                         float scale, int window, long long q_rs,
                         long long kv_rs, long long do_rs, long long dq_rs,
                         const float* rope_cos, const float* rope_sin,
-                        hipStream_t stream);
+                        const int* doc_start, hipStream_t stream);
 void acco_attn_bwd32_dkv(const void* q, const void* k, const void* v,
                          const void* dO, const float* lse,
                          const float* delta, void* dk, void* dv, int B,
                          int S, int H, int Hkv, int D, float scale,
                          int window, long long q_rs, long long kv_rs,
-                         long long do_rs, hipStream_t stream);
+                         long long do_rs, const int* doc_end,
+                         hipStream_t stream);
 
 // ---- delta.hip
 void acco_attn_delta(const void* dO, const void* O, float* delta, long long B,

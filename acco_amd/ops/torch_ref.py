@@ -75,9 +75,41 @@ def rope_apply(q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor,
     return q2, k2
 
 
+def doc_start_from_eos(input_ids: torch.Tensor,
+                       eos_token_id: int) -> torch.Tensor:
+    """Document boundaries of packed rows: int32 [B, S], entry (b, s) is the
+    index of the first token of the document that holds token s. A document
+    ends with its EOS (the EOS belongs to it); the next token starts a new
+    one. Non-decreasing along s, 0 <= out[b, s] <= s, and
+    out[b, out[b, s]] == out[b, s]. Plain torch ops, no host sync."""
+    B, S = input_ids.shape
+    pos = torch.arange(S, device=input_ids.device)
+    starts = torch.zeros(B, S, dtype=torch.long, device=input_ids.device)
+    # position s starts a document iff token s-1 is an EOS
+    starts[:, 1:] = (input_ids[:, :-1] == eos_token_id) * pos[1:]
+    return torch.cummax(starts, dim=1).values.to(torch.int32)
+
+
+def doc_end_from_start(doc_start: torch.Tensor) -> torch.Tensor:
+    """The key-side twin of doc_start: int32 [B, S], entry (b, s) is the
+    EXCLUSIVE end of the document that holds token s (the next document's
+    start, or S). The dkv attention kernel masks with it."""
+    B, S = doc_start.shape
+    ds = doc_start.long()
+    pos = torch.arange(S, device=doc_start.device)
+    # a document's last token is followed by a token with another start (or
+    # by the row's end); its end is the running minimum from the right
+    nxt = torch.full((B, S), S, dtype=torch.long, device=doc_start.device)
+    is_last = ds[:, 1:] != ds[:, :-1]
+    nxt[:, :-1] = torch.where(is_last, pos[1:], nxt[:, :-1])
+    end = torch.flip(torch.cummin(torch.flip(nxt, [1]), dim=1).values, [1])
+    return end.to(torch.int32)
+
+
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                      scale: Optional[float] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
+                     window: Optional[int] = None,
+                     doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal (optionally banded/local) attention.
 
     q: [B, S, H, D]; k, v: [B, S, Hkv, D] (GQA: H a multiple of Hkv) —
@@ -85,6 +117,9 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     `scale=None` → 1/sqrt(D); GPT-Neo passes scale=1.0 (it does not scale).
     `window` (GPT-Neo local layers, window_size=256): query i attends to
     keys j with i-window < j <= i.
+    `doc_start` (int [B, S], see doc_start_from_eos): query i attends only
+    to keys j >= doc_start[b, i], i.e. never across a document boundary of
+    a packed row; it combines with `window`.
     """
     B, S, H, D = q.shape
     Hkv = k.shape[2]
@@ -102,6 +137,9 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     mask = idx[None, :] > idx[:, None]           # future → masked
     if window is not None:
         mask = mask | (idx[None, :] <= idx[:, None] - window)
+    if doc_start is not None:
+        lo = doc_start.to(device=q.device, dtype=idx.dtype)   # [B, S] by query
+        mask = mask[None, None] | (idx[None, None, None, :] < lo[:, None, :, None])
     scores = scores.masked_fill(mask, float("-inf"))
     probs = torch.softmax(scores, dim=-1)
     out = torch.matmul(probs, v.float()).to(q.dtype)

@@ -6,6 +6,15 @@ the same token count. Next to the times it prints what the placement of the
 workgroups on the 8 XCDs predicts: the tile-iterations of the heaviest class
 id % 8 over the mean, for the 2-D (row block, head) grid the kernels used to
 launch and for the order they launch now (attn_block_order).
+
+--doc-len N lays documents of N tokens over the shape (N = S: one document,
+the DOC kernels with nothing to mask) and times the plain and the DOC path
+in this process, alternating (plain, DOC, plain, DOC, plain): the three
+repeats of the plain path give the run-to-run spread to read the DOC times
+against.
+Next to each time it prints the tile iterations the kernels' ranges predict,
+per workgroup loop ("staged": every tile a block loads) and per wave
+("computed": the tiles a wave does not skip).
 """
 
 import os
@@ -44,6 +53,77 @@ def placement_prediction(B, S, H):
     return out
 
 
+def tile_iterations(S, doc_len):
+    """Predicted tile iterations of one (b, h) for documents of doc_len
+    tokens (doc_len = None: the plain kernels), from the ranges of
+    attention_common.h: {kernel: (staged, computed)}."""
+    nt = S // TILE
+    ds = [(s // doc_len) * doc_len if doc_len else 0 for s in range(S)]
+    de = [min(d + doc_len, S) if doc_len else S for d in ds]
+    waves = BLOCK_ROWS // 32
+    fwd_staged = fwd_comp = dkv_staged = dkv_comp = 0
+    for blk in range(S // BLOCK_ROWS):
+        r0 = blk * BLOCK_ROWS
+        # forward / dq: kv tiles of a q block
+        j_lo = min(ds[r0] // TILE, nt - 1)
+        j_hi = (r0 + BLOCK_ROWS - 1) // TILE
+        fwd_staged += max(0, j_hi - j_lo + 1)
+        # dkv: q tiles of a kv block
+        qt_lo = r0 // TILE
+        qt_hi = min(nt - 1, (de[r0 + BLOCK_ROWS - 1] - 1) // TILE)
+        dkv_staged += max(0, qt_hi - qt_lo + 1)
+        for w in range(waves):
+            w0 = r0 + 32 * w
+            fwd_comp += sum(1 for j in range(j_lo, j_hi + 1)
+                            if j * TILE <= w0 + 31
+                            and j * TILE + TILE - 1 >= ds[w0])
+            dkv_comp += sum(1 for t in range(qt_lo, qt_hi + 1)
+                            if t * TILE + TILE - 1 >= w0
+                            and t * TILE < de[w0 + 31])
+    return {"fwd": (fwd_staged, fwd_comp), "dq": (fwd_staged, fwd_comp),
+            "dkv": (dkv_staged, dkv_comp)}
+
+
+def time_paths(q, k, v, do, sc, doc, iters=1000):
+    """(fwd ms, bwd ms) of one path; doc = () or (doc_start, doc_end)."""
+    ext = ops.hip_ext()
+    o, l = ext.attn_fwd(q, k, v, sc, 0, *doc[:1])
+    delta = ext.attn_delta(do, o)
+    for _ in range(3):
+        ext.attn_fwd(q, k, v, sc, 0, *doc[:1])
+        ext.attn_bwd(q, k, v, do, l, delta, sc, 0, *doc)
+    torch.cuda.synchronize()
+    t = time.time()
+    for _ in range(iters):
+        ext.attn_fwd(q, k, v, sc, 0, *doc[:1])
+    torch.cuda.synchronize()
+    dt_f = (time.time() - t) / iters
+    t = time.time()
+    for _ in range(iters):
+        ext.attn_bwd(q, k, v, do, l, delta, sc, 0, *doc)
+    torch.cuda.synchronize()
+    return dt_f * 1e3, (time.time() - t) / iters * 1e3
+
+
+def doc_comparison(q, k, v, do, sc, doc_len):
+    B, S = q.shape[:2]
+    pos = torch.arange(S, device="cuda")
+    ds = ((pos // doc_len) * doc_len).to(torch.int32).expand(B, S).contiguous()
+    de = ops.doc_end_from_start(ds)
+    plain_it, doc_it = tile_iterations(S, None), tile_iterations(S, doc_len)
+    print(f"doc-len {doc_len}: {(S + doc_len - 1) // doc_len} documents per "
+          "row; tile iterations per (b, h), staged / computed:")
+    for kern in ("fwd", "dq", "dkv"):
+        print(f"  {kern:4s} plain {plain_it[kern][0]:4d} / "
+              f"{plain_it[kern][1]:4d}   doc {doc_it[kern][0]:4d} / "
+              f"{doc_it[kern][1]:4d}")
+    for rep in range(5):
+        doc = (ds, de) if rep % 2 else ()
+        f, b = time_paths(q, k, v, do, sc, doc)
+        print(f"{'doc  ' if doc else 'plain'} #{rep // 2}: fwd {f:.3f} ms  "
+              f"bwd {b:.3f} ms")
+
+
 def main():
     torch.manual_seed(0)
     B, S, H, Hkv, Dh = 8, 1024, 32, 8, 64
@@ -63,6 +143,12 @@ def main():
     v = torch.randn(B, S, Hkv, Dh, device="cuda").bfloat16()
     do = torch.randn(B, S, H, Dh, device="cuda").bfloat16()
     sc = Dh ** -0.5
+    if "--doc-len" in sys.argv:
+        doc_len = int(sys.argv[sys.argv.index("--doc-len") + 1])
+        if not (0 < doc_len <= S and S % BLOCK_ROWS == 0):
+            raise SystemExit("--doc-len needs 0 < N <= S and S % 256 == 0")
+        doc_comparison(q, k, v, do, sc, doc_len)
+        return
     o, l = ops.hip_ext().attn_fwd(q, k, v, sc, 0)
     delta = (do.float() * o.float()).sum(-1).permute(0, 2, 1).contiguous()
 

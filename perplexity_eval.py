@@ -18,7 +18,9 @@ import torch
 from torch.utils.data import DataLoader
 
 from acco_amd.config import load_config
-from acco_amd.data.synthetic import SyntheticCausalLMDataset, collate_input_ids
+from acco_amd.data.synthetic import (DocMaskCollator,
+                                     SyntheticCausalLMDataset,
+                                     collate_input_ids, resolve_doc_mask_eos)
 from acco_amd.models import build_model
 
 
@@ -33,7 +35,11 @@ def compute_perplexity(model, dataloader, device, dtype=torch.float32,
         if max_batches is not None and i >= max_batches:
             break
         ids = batch["input_ids"].to(device)
-        loss, _ = model(ids, labels=ids)
+        if "doc_start" in batch:         # train.doc_mask
+            loss, _ = model(ids, labels=ids,
+                            doc_start=batch["doc_start"].to(device))
+        else:
+            loss, _ = model(ids, labels=ids)
         n_tok = ids.shape[0] * (ids.shape[1] - 1)
         total_nll += float(loss) * n_tok
         total_tokens += n_tok
@@ -53,6 +59,7 @@ def main(argv=None):
         model.load_state_dict(sd)
     model = model.to(device, dtype=dtype)
 
+    tok = None
     if cfg.data.get("kind") == "synthetic":
         ds = SyntheticCausalLMDataset(cfg.data.n_eval_sequences or 64,
                                       cfg.train.max_length,
@@ -67,8 +74,11 @@ def main(argv=None):
         ds = raw.map(make_tokenize_const_len_fn(tok, "text",
                                                 cfg.train.max_length),
                      batched=True, remove_columns=raw.column_names)
+    eos = resolve_doc_mask_eos(cfg.train.get("doc_mask", False), tok, model)
     dl = DataLoader(ds, batch_size=cfg.train.batch_size,
-                    collate_fn=collate_input_ids, drop_last=True)
+                    collate_fn=(collate_input_ids if eos is None
+                                else DocMaskCollator(eos)),
+                    drop_last=True)
     ppl = compute_perplexity(model, dl, device)
     print(f"perplexity: {ppl:.4f}")
     return ppl
