@@ -23,6 +23,26 @@ namespace {
 typedef float f4_ __attribute__((ext_vector_type(4)));
 typedef unsigned short u4_ __attribute__((ext_vector_type(4)));
 
+struct AdamWCoef {
+  float s, beta1, beta2, eps, wd_factor, lr_bc1, inv_bc2_sqrt;
+};
+
+// One element's update. Every rounding is spelled out and the compiler may
+// not contract across them: left to itself it fused p·wd - q and β2·v + ...
+// in some instantiations and loops and not in others, so a tentative step
+// (COMMIT = false) emitted parameters that differed in the last fp32 bit
+// from the commit step of the same state, and the scalar tail from the
+// vector loop. The form kept is the one the bf16 commit vector loop had.
+ACCO_DEV void adamw_update(const AdamWCoef& c, float g, float& p, float& m,
+                           float& v) {
+#pragma clang fp contract(off)
+  const float gk = g * c.s;
+  m = __builtin_fmaf(c.beta1, m, (1.0f - c.beta1) * gk);
+  v = c.beta2 * v + ((1.0f - c.beta2) * gk) * gk;
+  const float denom = __builtin_fmaf(sqrtf(v), c.inv_bc2_sqrt, c.eps);
+  p = __builtin_fmaf(c.wd_factor, p, -((c.lr_bc1 * m) / denom));
+}
+
 // p/m/v/g/out are each streamed exactly once per round: nontemporal
 // loads/stores keep the ~3.4 GB working set out of L2 (guide: streaming
 // kernels should not thrash caches shared with the concurrently running
@@ -38,7 +58,9 @@ __global__ void fused_adamw_kernel(
     float wd_factor,                 // (1 - lr*weight_decay)
     float inv_bc1, float inv_bc2_sqrt)
 {
-  const float s = (scale_dev != nullptr) ? (scale * *scale_dev) : scale;
+  const AdamWCoef c = {(scale_dev != nullptr) ? (scale * *scale_dev) : scale,
+                       beta1, beta2, eps, wd_factor, lr * inv_bc1,
+                       inv_bc2_sqrt};
   const long long i0 = (long long)(blockIdx.x) * blockDim.x + threadIdx.x;
   const long long stride = (long long)gridDim.x * blockDim.x;
   const long long n4 = n >> 2;
@@ -50,13 +72,8 @@ __global__ void fused_adamw_kernel(
     float po[4], mo[4], vo[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      float gk = gf[k] * s;
-      float pk = pf[k] * wd_factor;
-      float mk = beta1 * mf[k] + (1.0f - beta1) * gk;
-      float vk = beta2 * vf[k] + (1.0f - beta2) * gk * gk;
-      float denom = sqrtf(vk) * inv_bc2_sqrt + eps;
-      pk -= lr * inv_bc1 * mk / denom;
-      po[k] = pk; mo[k] = mk; vo[k] = vk;
+      po[k] = pf[k]; mo[k] = mf[k]; vo[k] = vf[k];
+      adamw_update(c, gf[k], po[k], mo[k], vo[k]);
     }
     if constexpr (COMMIT) {
       __builtin_nontemporal_store(f4_{po[0], po[1], po[2], po[3]},
@@ -120,12 +137,8 @@ __global__ void fused_adamw_kernel(
     float gk;
     if constexpr (sizeof(Tbuf) == 2) gk = bf16_to_f32(((const unsigned short*)g)[i]);
     else                             gk = ((const float*)g)[i];
-    gk *= s;
-    float pk = p[i] * wd_factor;
-    float mk = beta1 * m[i] + (1.0f - beta1) * gk;
-    float vk = beta2 * v[i] + (1.0f - beta2) * gk * gk;
-    float denom = sqrtf(vk) * inv_bc2_sqrt + eps;
-    pk -= lr * inv_bc1 * mk / denom;
+    float pk = p[i], mk = m[i], vk = v[i];
+    adamw_update(c, gk, pk, mk, vk);
     if constexpr (COMMIT) { p[i] = pk; m[i] = mk; v[i] = vk; }
     if (out != nullptr) {
       if constexpr (sizeof(Tbuf) == 2) ((unsigned short*)out)[i] = f32_to_bf16(pk);

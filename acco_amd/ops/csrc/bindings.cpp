@@ -5,40 +5,80 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 #include "kernels.h"
 
 namespace {
 
 using u16 = unsigned short;
 
+// base pointer on a multiple of the vector width the kernel loads with
+static bool aligned_to(const at::Tensor& t, size_t bytes) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0;
+}
+
+// The argument contract of the fused AdamW: p, m, v contiguous CUDA fp32 of
+// one numel on one device, 16-byte aligned (float4 accesses); g (and out,
+// when given) contiguous bf16 or fp32 of that numel on that device, aligned
+// to 4 elements; scale_dev, when given, one fp32 on that device.
 void fused_adamw(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                  int64_t step, double lr, double beta1, double beta2,
                  double eps, double weight_decay, double scale,
                  at::Tensor scale_dev, at::Tensor out, bool commit) {
-  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous());
-  TORCH_CHECK(m.sizes() == p.sizes() && v.sizes() == p.sizes());
-  TORCH_CHECK(g.numel() == p.numel() && g.is_contiguous());
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(),
+              "p must be contiguous CUDA fp32");
+  auto check_state = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == p.device() &&
+                t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                t.numel() == p.numel(), name, " must be contiguous CUDA fp32 "
+                "with p's numel (", p.numel(), ") on ", p.device(), ", got ",
+                t.scalar_type(), " ", t.sizes(), " on ", t.device());
+  };
+  check_state(m, "m");
+  check_state(v, "v");
+  TORCH_CHECK(step >= 0, "step must be >= 0, got ", step);
   const bool bf16 = g.scalar_type() == at::kBFloat16;
   TORCH_CHECK(bf16 || g.scalar_type() == at::kFloat,
               "grad must be bf16 or fp32");
+  TORCH_CHECK(g.device() == p.device() && g.numel() == p.numel() &&
+              g.is_contiguous(), "g must be contiguous with p's numel (",
+              p.numel(), ") on ", p.device(), ", got ", g.sizes(), " on ",
+              g.device());
+  const size_t buf_align = bf16 ? 8 : 16;
+  TORCH_CHECK(aligned_to(p, 16) && aligned_to(m, 16) && aligned_to(v, 16),
+              "p, m, v must be 16-byte aligned");
+  TORCH_CHECK(aligned_to(g, buf_align), "g must be ", buf_align,
+              "-byte aligned");
   void* out_ptr = nullptr;
   if (out.numel() > 0) {
-    TORCH_CHECK(out.numel() == p.numel() && out.is_contiguous());
+    TORCH_CHECK(out.device() == p.device() && out.numel() == p.numel() &&
+                out.is_contiguous(), "out must be contiguous with p's numel (",
+                p.numel(), ") on ", p.device(), ", got ", out.sizes(), " on ",
+                out.device());
     TORCH_CHECK(out.scalar_type() == g.scalar_type(),
                 "out dtype must match grad (com-buffer) dtype");
+    TORCH_CHECK(aligned_to(out, buf_align), "out must be ", buf_align,
+                "-byte aligned");
     out_ptr = out.data_ptr();
   }
   const float* sd = nullptr;
   if (scale_dev.numel() > 0) {
-    TORCH_CHECK(scale_dev.scalar_type() == at::kFloat && scale_dev.is_cuda());
+    TORCH_CHECK(scale_dev.scalar_type() == at::kFloat && scale_dev.is_cuda() &&
+                scale_dev.device() == p.device() && scale_dev.numel() == 1,
+                "scale_dev must be one fp32 on ", p.device(), ", got ",
+                scale_dev.scalar_type(), " ", scale_dev.sizes(), " on ",
+                scale_dev.device());
     sd = scale_dev.data_ptr<float>();
   }
+  if (p.numel() == 0) return;
   auto stream = at::hip::getCurrentHIPStream();
   acco_fused_adamw_launch(p.data_ptr(), g.data_ptr(), m.data_ptr(),
                           v.data_ptr(), out_ptr, sd, (long long)p.numel(),
                           bf16, commit, (float)scale, (float)lr, (float)beta1,
                           (float)beta2, (float)eps, (float)weight_decay,
                           step + 1, stream.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 at::Tensor colsum(at::Tensor in) {
@@ -76,69 +116,111 @@ static void check_rope_table(const at::Tensor& cos_t, const at::Tensor& sin_t,
 }
 
 // ---- SwiGLU / gelu_new
+// The input of an elementwise kernel: contiguous CUDA bf16, at least 1-D,
+// whole 8-element vectors per row (`last_mult` = 16 for the packed [.., 2I]
+// layout, whose two halves are each read as vectors).
+static void check_ew_input(const at::Tensor& x, const char* name,
+                           int64_t last_mult) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+              x.is_contiguous(), name, " must be contiguous CUDA bf16");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) % last_mult == 0 &&
+              x.numel() % 8 == 0, name, " must be at least 1-D with a last "
+              "dimension that is a multiple of ", last_mult, ", got ",
+              x.sizes());
+}
+
+// `t` (u against g, dout against the output): contiguous CUDA bf16 of
+// exactly `sizes` on ref's device
+static void check_ew_like(const at::Tensor& ref, at::IntArrayRef sizes,
+                          const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+              t.is_contiguous(), name, " must be contiguous CUDA bf16");
+  TORCH_CHECK(t.device() == ref.device() && t.sizes() == sizes, name,
+              ": expected ", sizes, " on ", ref.device(), ", got ", t.sizes(),
+              " on ", t.device());
+}
+
 at::Tensor swiglu_fwd(at::Tensor g, at::Tensor u) {
-  CHECK_BF16_CONTIG(g); CHECK_BF16_CONTIG(u);
-  TORCH_CHECK(g.numel() == u.numel() && g.numel() % 8 == 0);
+  check_ew_input(g, "g", 8);
+  check_ew_like(g, g.sizes(), u, "u");
   const int I = (int)g.size(-1);
-  TORCH_CHECK(I % 8 == 0);
   auto out = at::empty_like(g);
+  if (g.numel() == 0) return out;
   acco_swiglu_fwd(g.data_ptr(), u.data_ptr(), out.data_ptr(), g.numel(),
                   I, I / 8, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
 std::vector<at::Tensor> swiglu_bwd(at::Tensor dout, at::Tensor g, at::Tensor u) {
-  CHECK_BF16_CONTIG(dout); CHECK_BF16_CONTIG(g); CHECK_BF16_CONTIG(u);
+  check_ew_input(g, "g", 8);
+  check_ew_like(g, g.sizes(), u, "u");
+  check_ew_like(g, g.sizes(), dout, "dout");
   const int I = (int)g.size(-1);
   auto dg = at::empty_like(g);
   auto du = at::empty_like(u);
+  if (g.numel() == 0) return {dg, du};
   acco_swiglu_bwd(dout.data_ptr(), g.data_ptr(), u.data_ptr(), dg.data_ptr(),
                   du.data_ptr(), g.numel(), I, I / 8, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dg, du};
+}
+
+// sizes of the packed SwiGLU's output: gu's with the last dimension halved
+static std::vector<int64_t> packed_out_sizes(const at::Tensor& gu) {
+  auto sizes = gu.sizes().vec();
+  sizes.back() /= 2;
+  return sizes;
 }
 
 // SwiGLU over the packed [rows, 2I] fused gate_up projection output:
 // out = silu(gu[:, :I]) * gu[:, I:]; backward emits dgu in one pass
 // (no torch.split → no contiguous copies forward, no cat backward).
 at::Tensor swiglu_packed_fwd(at::Tensor gu) {
-  CHECK_BF16_CONTIG(gu);
+  check_ew_input(gu, "gu", 16);
   const int twoI = (int)gu.size(-1);
-  TORCH_CHECK(twoI % 16 == 0);
   const int I = twoI / 2;
-  auto sizes = gu.sizes().vec();
-  sizes.back() = I;
-  auto out = at::empty(sizes, gu.options());
+  auto out = at::empty(packed_out_sizes(gu), gu.options());
+  if (gu.numel() == 0) return out;
   const u16* base = (const u16*)gu.data_ptr();
   acco_swiglu_fwd(base, base + I, out.data_ptr(), gu.numel() / 2, I,
                   twoI / 8, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
 at::Tensor swiglu_packed_bwd(at::Tensor dout, at::Tensor gu) {
-  CHECK_BF16_CONTIG(dout); CHECK_BF16_CONTIG(gu);
+  check_ew_input(gu, "gu", 16);
+  check_ew_like(gu, packed_out_sizes(gu), dout, "dout");
   const int twoI = (int)gu.size(-1);
   const int I = twoI / 2;
   auto dgu = at::empty_like(gu);
+  if (gu.numel() == 0) return dgu;
   const u16* base = (const u16*)gu.data_ptr();
   u16* dbase = (u16*)dgu.data_ptr();
   acco_swiglu_bwd(dout.data_ptr(), base, base + I, dbase, dbase + I,
                   gu.numel() / 2, I, twoI / 8, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dgu;
 }
 
 at::Tensor gelu_fwd(at::Tensor x) {
-  CHECK_BF16_CONTIG(x);
-  TORCH_CHECK(x.numel() % 8 == 0);
+  check_ew_input(x, "x", 8);
   auto out = at::empty_like(x);
+  if (x.numel() == 0) return out;
   acco_gelu_fwd(x.data_ptr(), out.data_ptr(), x.numel(), cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
 at::Tensor gelu_bwd(at::Tensor dout, at::Tensor x) {
-  CHECK_BF16_CONTIG(dout); CHECK_BF16_CONTIG(x);
+  check_ew_input(x, "x", 8);
+  check_ew_like(x, x.sizes(), dout, "dout");
   auto dx = at::empty_like(x);
+  if (x.numel() == 0) return dx;
   acco_gelu_bwd(dout.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(),
                 cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dx;
 }
 
@@ -284,68 +366,101 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x,
 at::Tensor rope_fwd(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t,
                     bool bwd) {
   CHECK_BF16_CONTIG(x);
-  TORCH_CHECK(x.dim() == 4);
-  TORCH_CHECK(cos_t.scalar_type() == at::kFloat && cos_t.is_contiguous());
-  TORCH_CHECK(sin_t.scalar_type() == at::kFloat && sin_t.is_contiguous());
+  TORCH_CHECK(x.dim() == 4 && x.size(3) % 8 == 0 && x.size(1) < (1LL << 31),
+              "x must be [B,S,H,D] with D % 8 == 0, got ", x.sizes());
   const long long B = x.size(0);
   const int S = (int)x.size(1), H = (int)x.size(2), D = (int)x.size(3);
-  TORCH_CHECK(D % 8 == 0 && cos_t.size(0) >= S && cos_t.size(1) == D);
+  check_rope_table(cos_t, sin_t, S, D, x);
   auto y = at::empty_like(x);
+  if (x.numel() == 0) return y;
   acco_rope(x.data_ptr(), y.data_ptr(), cos_t.data_ptr<float>(),
             sin_t.data_ptr<float>(), B, S, H, D, bwd,
             (long long)H * D, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return y;
 }
 
 // ---- fused shifted causal-LM CE
+struct CeShape { long long T; int S, V; };
+
+// The argument contract of the CE entry points: logits contiguous CUDA bf16
+// [B, S, V]; labels contiguous int64 [B, S] on the logits' device; in the
+// backward, lse contiguous fp32 with one element per token and acc fp32
+// {loss_sum, n_valid, ...}, both on that device.
+static CeShape check_ce_args(const at::Tensor& logits,
+                             const at::Tensor& labels,
+                             const at::Tensor* lse = nullptr,
+                             const at::Tensor* acc = nullptr) {
+  CHECK_BF16_CONTIG(logits);
+  TORCH_CHECK(logits.dim() == 3 && logits.size(1) < (1LL << 31) &&
+              logits.size(2) > 0 && logits.size(2) < (1LL << 31),
+              "logits must be [B,S,V] with V > 0, got ", logits.sizes());
+  const int64_t B = logits.size(0), S = logits.size(1);
+  TORCH_CHECK(labels.is_cuda() && labels.device() == logits.device() &&
+              labels.scalar_type() == at::kLong && labels.is_contiguous() &&
+              labels.dim() == 2 && labels.size(0) == B && labels.size(1) == S,
+              "labels must be contiguous int64 [B, S] = [", B, ", ", S,
+              "] on ", logits.device(), ", got ", labels.scalar_type(), " ",
+              labels.sizes(), " on ", labels.device());
+  if (lse != nullptr)
+    TORCH_CHECK(lse->is_cuda() && lse->device() == logits.device() &&
+                lse->scalar_type() == at::kFloat && lse->is_contiguous() &&
+                lse->numel() == B * S, "lse must be contiguous CUDA fp32 with "
+                "B*S = ", B * S, " elements on ", logits.device(), ", got ",
+                lse->scalar_type(), " ", lse->sizes(), " on ", lse->device());
+  if (acc != nullptr)
+    TORCH_CHECK(acc->is_cuda() && acc->device() == logits.device() &&
+                acc->scalar_type() == at::kFloat && acc->is_contiguous() &&
+                acc->numel() >= 2, "acc must be contiguous CUDA fp32 "
+                "{loss_sum, n_valid} on ", logits.device(), ", got ",
+                acc->scalar_type(), " ", acc->sizes(), " on ", acc->device());
+  return {(long long)(B * S), (int)S, (int)logits.size(2)};
+}
+
 std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor labels,
                                double epsilon) {
-  CHECK_BF16_CONTIG(logits);
-  TORCH_CHECK(logits.dim() == 3 && labels.dim() == 2);
-  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous());
-  const long long Bn = logits.size(0);
-  const int S = (int)logits.size(1), V = (int)logits.size(2);
-  const long long T = Bn * S;
+  const auto [T, S, V] = check_ce_args(logits, labels);
   auto lse = at::empty({T}, logits.options().dtype(at::kFloat));
   // 128 accumulator shards (atomic-contention fix in ce.hip) reduced here
   auto accs = at::zeros({128, 2}, logits.options().dtype(at::kFloat));
+  if (T == 0) return {accs.sum(0), lse};
   acco_ce_fwd(logits.data_ptr(),
               reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
               lse.data_ptr<float>(), accs.data_ptr<float>(), T, S, V,
               (float)epsilon, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {accs.sum(0), lse};
 }
 
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor lse,
                   at::Tensor acc, double dloss, double epsilon) {
-  CHECK_BF16_CONTIG(logits);
-  const long long Bn = logits.size(0);
-  const int S = (int)logits.size(1), V = (int)logits.size(2);
-  const long long T = Bn * S;
+  const auto [T, S, V] = check_ce_args(logits, labels, &lse, &acc);
   auto dlogits = at::empty_like(logits);
+  if (T == 0) return dlogits;
   acco_ce_bwd(logits.data_ptr(),
               reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
               lse.data_ptr<float>(), dlogits.data_ptr(),
               acc.data_ptr<float>(), (float)dloss, nullptr, T, S, V,
               (float)epsilon, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dlogits;
 }
 
 // dloss read from a 1-elem fp32 device tensor: no D2H sync in backward
 at::Tensor ce_bwd_dev(at::Tensor logits, at::Tensor labels, at::Tensor lse,
                       at::Tensor acc, at::Tensor dloss_dev, double epsilon) {
-  CHECK_BF16_CONTIG(logits);
-  TORCH_CHECK(dloss_dev.is_cuda() && dloss_dev.scalar_type() == at::kFloat &&
-              dloss_dev.numel() == 1);
-  const long long Bn = logits.size(0);
-  const int S = (int)logits.size(1), V = (int)logits.size(2);
-  const long long T = Bn * S;
+  const auto [T, S, V] = check_ce_args(logits, labels, &lse, &acc);
+  TORCH_CHECK(dloss_dev.is_cuda() && dloss_dev.device() == logits.device() &&
+              dloss_dev.scalar_type() == at::kFloat && dloss_dev.numel() == 1,
+              "dloss_dev must be one fp32 on ", logits.device());
   auto dlogits = at::empty_like(logits);
+  if (T == 0) return dlogits;
   acco_ce_bwd(logits.data_ptr(),
               reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
               lse.data_ptr<float>(), dlogits.data_ptr(),
               acc.data_ptr<float>(), 0.0f, dloss_dev.data_ptr<float>(), T, S,
               V, (float)epsilon, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dlogits;
 }
 
@@ -611,11 +726,18 @@ void attn_gqa_reduce_rope(at::Tensor dkq, at::Tensor dvq, at::Tensor dqkv,
 // ---- experimental NT GEMM (C = A · B^T, bf16; bench/refcheck only)
 at::Tensor gemm_nt(at::Tensor A, at::Tensor B) {
   CHECK_BF16_CONTIG(A); CHECK_BF16_CONTIG(B);
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && B.device() == A.device(),
+              "need A [M,K] and B [N,K] on one device, got ", A.sizes(),
+              " on ", A.device(), " and ", B.sizes(), " on ", B.device());
   const int M = (int)A.size(0), K = (int)A.size(1), N = (int)B.size(0);
-  TORCH_CHECK(B.size(1) == K && M % 128 == 0 && N % 128 == 0 && K % 64 == 0);
+  TORCH_CHECK(B.size(1) == K && M % 128 == 0 && N % 128 == 0 && K % 64 == 0,
+              "need M % 128 == 0, N % 128 == 0, K % 64 == 0 and one K, got ",
+              A.sizes(), " and ", B.sizes());
+  if (M == 0 || N == 0 || K == 0) return at::zeros({M, N}, A.options());
   auto C = at::empty({M, N}, A.options());
   acco_gemm_nt(A.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K,
                cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return C;
 }
 
@@ -623,18 +745,34 @@ at::Tensor gemm_nt(at::Tensor A, at::Tensor B) {
 // grad produced with ZERO split/cat copies). qkv: [B, S, W] contiguous with
 // W >= (H + 2*Hkv)*D, sections at the given offsets (check_packed_layout);
 // D in {64, 128}, S%256==0 (v4 kernels only).
+
+// RoPE of one section (Hsec heads of width D at column `off`) of src [B,S,W]
+// into the same section of dst; off a multiple of 4 (8-byte vectors).
 std::vector<at::Tensor> rope_packed(at::Tensor src, at::Tensor dst,
                                     at::Tensor cos_t, at::Tensor sin_t,
                                     int64_t off, int64_t Hsec, int64_t D,
                                     bool bwd) {
   CHECK_BF16_CONTIG(src); CHECK_BF16_CONTIG(dst);
+  TORCH_CHECK(src.dim() == 3 && src.size(1) < (1LL << 31),
+              "src must be [B,S,W], got ", src.sizes());
+  TORCH_CHECK(dst.device() == src.device() && dst.sizes() == src.sizes(),
+              "dst: expected ", src.sizes(), " on ", src.device(), ", got ",
+              dst.sizes(), " on ", dst.device());
   const long long B = src.size(0);
   const int S = (int)src.size(1);
   const long long W = src.size(2);
+  TORCH_CHECK(D > 0 && D % 8 == 0 && Hsec > 0 && Hsec < (1LL << 31) / D,
+              "need D % 8 == 0 and Hsec > 0, got D=", D, " Hsec=", Hsec);
+  TORCH_CHECK(off >= 0 && off % 4 == 0 && off + Hsec * D <= W, "section [",
+              off, ", ", off + Hsec * D, ") must start at a multiple of 4 "
+              "inside W=", W);
+  check_rope_table(cos_t, sin_t, S, D, src);
+  if (src.numel() == 0) return {dst};
   acco_rope((const u16*)src.data_ptr() + off,
             (u16*)dst.data_ptr() + off, cos_t.data_ptr<float>(),
             sin_t.data_ptr<float>(), B, S, (int)Hsec, (int)D, bwd, W,
             cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dst};
 }
 

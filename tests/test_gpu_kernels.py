@@ -102,13 +102,16 @@ def test_rope_fwd_bwd(D):
     assert _close_bf16(k2, k2r)
     dq = torch.randn_like(q2)
     dk = torch.randn_like(k2)
-    (q2 * dq.detach()).sum().backward(retain_graph=True)
+    ((q2 * dq.detach()).sum() + (k2 * dk.detach()).sum()).backward(
+        retain_graph=True)
     # grad check via autograd on the fp32 reference
     q32 = q.detach().float().requires_grad_(True)
     k32 = k.detach().float().requires_grad_(True)
     q2f, k2f = torch_ref.rope_apply(q32, k32, cos, sin)
-    (q2f * dq.detach().float()).sum().backward()
+    ((q2f * dq.detach().float()).sum()
+     + (k2f * dk.detach().float()).sum()).backward()
     assert _close_bf16(q.grad, q32.grad)
+    assert _close_bf16(k.grad, k32.grad)
 
 
 def test_ce_fwd_bwd():
