@@ -229,7 +229,7 @@ struct NormShape { long long R; int D; };
 
 // The argument contract of every norm entry point, forward and backward:
 // D % 8 == 0 (16-byte vector loads), D <= 16384 (8 chunks of 256 lanes),
-// whole rows; each `like_x` that is given (dy, res, dadd) is bf16 of x's
+// x's last dimension is D = w.numel(); each `like_x` that is given (dy, res, dadd) is bf16 of x's
 // numel on x's device; every saved row statistic is a contiguous fp32 [R]
 // on x's device.
 static NormShape check_norm_args(
@@ -242,6 +242,9 @@ static NormShape check_norm_args(
               w.device() == x.device(),
               "norm width must be a multiple of 8, at most 16384, and divide "
               "x.numel(); got D=", D, " x.numel()=", x.numel());
+  // a w of half the width divides x.numel() too and would norm half rows
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == D, "w must hold one element per "
+              "column of x; got w.numel()=", D, " x ", x.sizes());
   const long long R = x.numel() / D;
   for (const auto& t : like_x)
     if (t.has_value()) {

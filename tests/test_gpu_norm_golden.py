@@ -37,6 +37,7 @@ DIMS = [256, 768, 1024, 2048, 2560, 4096, 8192, 16384]
 # the stored bf16 sum, and that rounding noise grows with sqrt(R); the add
 # tolerance was set at 132 rows. The plain cases at the same shapes run the
 # same dW code and pass the tighter plain tolerance.
+# test_gpu_norm_kernels.py runs these four against a reference of the bf16 sum.
 PARENT_MISSES_REFERENCE = {
     "rms_2048_8195_add": 1.118,
     "ln_256_4099_add": 0.4662,
