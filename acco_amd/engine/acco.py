@@ -51,6 +51,9 @@ class AccoEngine:
     comm         : collective backend (RCCL / gloo).
     forward_backward : callable(inputs) -> loss float tensor; must
         accumulate gradients into grads_arena (i.e. call loss.backward()).
+    max_grad_norm : clip the round's averaged gradient to this global L2
+        norm (None / 0 = off), like torch.nn.utils.clip_grad_norm_. Every
+        round, tentative or commit, clips the gradient it consumes.
     """
 
     def __init__(self, *, params_arena: torch.Tensor, grads_arena: torch.Tensor,
@@ -60,6 +63,7 @@ class AccoEngine:
                  next_batch: Callable[[], Dict],
                  n_grad_accumulation: int = 1,
                  grad_reduce_dtype: Optional[str] = None,
+                 max_grad_norm: Optional[float] = None,
                  log=None):
         self.params = params_arena
         self.grads = grads_arena
@@ -74,6 +78,11 @@ class AccoEngine:
         self.next_batch = next_batch
         self.n_acc = n_grad_accumulation
         self.log = log
+        # global grad-norm clipping runs on the optimizer's workspace; a
+        # value given here sets it there (None keeps the optimizer's own)
+        if max_grad_norm is not None:
+            opt.max_grad_norm = float(max_grad_norm or 0.0)
+        self._round_clip: Optional[dict] = None
 
         # the communication buffer (reference com_buffer, :244-269)
         self.com_buffer = torch.zeros(spec.total, dtype=params_arena.dtype,
@@ -196,14 +205,26 @@ class AccoEngine:
         per-bucket C3 reduce-scatter → fused sharded AdamW per bucket as its
         bucket lands (pipelined) → per-bucket C4 all-gather
         (reference communication_step :67-126). Returns the global grad
-        count of the round."""
+        count of the round.
+
+        With max_grad_norm set, the per-bucket sums of squares run as the
+        reduce-scatters land, then one scalar all-reduce yields the clip
+        coefficient on device (no host sync before the all-gathers are
+        issued). The cost is structural: the first AdamW now waits for the
+        LAST reduce-scatter instead of the first; the AdamW → all-gather
+        pipeline behind it is unchanged. The round's `grad_norm` (before
+        clipping) and `clip_coef` are appended to its com_log entry."""
         if advance_sched is None:
             advance_sched = commit
         t0 = time.time()
         with trace_range("acco/communication_round"):
             n = self._communication_round(commit, advance_sched)
-        self.com_log.append({"round": self.round_idx, "commit": commit,
-                             "t": time.time() - t0, "count": n})
+        entry = {"round": self.round_idx, "commit": commit,
+                 "t": time.time() - t0, "count": n}
+        if self._round_clip is not None:
+            entry.update(self._round_clip)
+            self._round_clip = None
+        self.com_log.append(entry)
         if self._debug_handoff:
             self._handoff_sum = self.com_buffer[:min(self.n, 1 << 20)].float().sum()
         return n
@@ -222,10 +243,21 @@ class AccoEngine:
         # grad averaging divides by the GLOBAL grad count (reference :85-98)
         inv_count = 1.0 / self.count_grad_this_round.float()
         lr = self.sched.lr()
+        grad_scale = inv_count
+        if self.opt.clipping:
+            # the norm is global, so no AdamW can start before the last
+            # bucket has landed: each bucket's sum of squares runs as its
+            # reduce-scatter lands (overlapping the remaining ones), then
+            # one scalar all-reduce, and the clip coefficient is folded into
+            # the device scale the AdamW kernel multiplies by anyway
+            for j in range(self.spec.nb):
+                rs[j].wait()
+                self.opt.accumulate_sumsq(j, buf)
+            grad_scale = self.opt.finalize_clip(self.comm, inv_count)
         ag = []
         for j in range(self.spec.nb):
             rs[j].wait()
-            self.opt.step_bucket(j, buf, grad_scale=inv_count,
+            self.opt.step_bucket(j, buf, grad_scale=grad_scale,
                                  commit=commit, lr=lr)
             ag.append(self.comm.all_gather_bucket_async(buf, self.spec, j,
                                                         self.rank))
@@ -235,6 +267,10 @@ class AccoEngine:
             self.com_buffer.copy_(buf)             # new params fp32 → bf16
         self.opt.finish_round(commit)
         n_global = int(self.count_grad_this_round.item())
+        if self.opt.clipping:
+            # read where the count is read: the stream is drained already
+            self._round_clip = {"grad_norm": float(self.opt.grad_norm.item()),
+                                "clip_coef": float(self.opt.clip_coef.item())}
         if advance_sched:
             self.sched.advance(n_global)
         return n_global

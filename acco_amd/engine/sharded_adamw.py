@@ -28,7 +28,8 @@ from acco_amd.parallel.comm import ShardSpec
 class ShardedAdamW:
     def __init__(self, spec: ShardSpec, rank: int, device: torch.device,
                  lr: float, betas=(0.9, 0.95), eps: float = 1e-8,
-                 weight_decay: float = 0.1):
+                 weight_decay: float = 0.1,
+                 max_grad_norm: Optional[float] = None):
         self.spec = spec
         self.rank = rank
         self.lr = float(lr)
@@ -39,6 +40,50 @@ class ShardedAdamW:
         self.p = torch.zeros(spec.owned, dtype=torch.float32, device=device)
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
+        # global grad-norm clipping (None / 0 = off): a [nb, partials]
+        # workspace of per-block sums of squares per gradient dtype, made on
+        # first use, and the scalars of the last clipped round, all on device
+        self.max_grad_norm = float(max_grad_norm or 0.0)
+        self._sumsq_ws: dict = {}
+        self._sumsq_used: Optional[torch.Tensor] = None
+        self.sumsq = torch.zeros(1, dtype=torch.float32, device=device)
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=device)
+        self.clip_coef = torch.ones(1, dtype=torch.float32, device=device)
+        self.clip_scale: Optional[torch.Tensor] = None
+
+    @property
+    def clipping(self) -> bool:
+        return self.max_grad_norm > 0.0
+
+    @torch.no_grad()
+    def accumulate_sumsq(self, j: int, buffer: torch.Tensor) -> None:
+        """Sum of squares of this rank's reduce-scattered segment of bucket
+        j of `buffer` (com buffer, its fp32 shadow or the DDP grad arena)
+        into row j of the workspace. Padding elements are zero in both
+        engines and add nothing."""
+        ws = self._sumsq_ws.get(buffer.dtype)
+        if ws is None:
+            n_part = ops.grad_sumsq_partials(self.spec.seg, buffer.dtype,
+                                             buffer.device)
+            ws = torch.empty(self.spec.nb, n_part, dtype=torch.float32,
+                             device=buffer.device)
+            self._sumsq_ws[buffer.dtype] = ws
+        ops.grad_sumsq(self.spec.seg_view(buffer, j, self.rank), ws[j])
+        self._sumsq_used = ws
+
+    @torch.no_grad()
+    def finalize_clip(self, comm, grad_scale: Union[float, torch.Tensor]
+                      ) -> torch.Tensor:
+        """After accumulate_sumsq on every bucket: this rank's sum of
+        squares, the scalar all-reduce over ranks (issued at the same point
+        of the round on every rank), then the clip coefficient folded into
+        `grad_scale`. Returns the 1-element scale tensor for step_bucket;
+        `grad_norm` and `clip_coef` stay on the device. No host sync."""
+        ops.sumsq_finalize(self._sumsq_used, self.sumsq)
+        comm.all_reduce_sum_async(self.sumsq).wait()
+        self.clip_scale, self.grad_norm, self.clip_coef = ops.clip_grad_scale(
+            self.sumsq, grad_scale, self.max_grad_norm)
+        return self.clip_scale
 
     @torch.no_grad()
     def init_master_from_buffer(self, buffer: torch.Tensor) -> None:

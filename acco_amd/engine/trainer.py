@@ -116,11 +116,14 @@ class DecoupledTrainer:
         # ---- optimizer / scheduler / engine
         self.sched = LRSchedule(args.learning_rate, args.warmup,
                                 self.nb_grad_tot, args.scheduler_name)
+        # train.max_grad_norm: global grad-norm clipping (0 / null = off)
+        self.max_grad_norm = float(getattr(args, "max_grad_norm", 0) or 0)
         self.opt = ShardedAdamW(self.spec, self.rank, self.device,
                                 lr=args.learning_rate,
                                 betas=(args.adam_beta1, args.adam_beta2),
                                 eps=float(getattr(args, "adam_eps", 1e-8) or 1e-8),
-                                weight_decay=args.weight_decay)
+                                weight_decay=args.weight_decay,
+                                max_grad_norm=self.max_grad_norm)
 
         if args.method_name == "ddp" or getattr(args, "run_baseline_ddp", False):
             self.loss_div = float(args.n_grad_accumulation)
@@ -139,6 +142,7 @@ class DecoupledTrainer:
                 next_batch=self.load_next_batch,
                 n_grad_accumulation=int(args.n_grad_accumulation),
                 grad_reduce_dtype=getattr(args, "grad_reduce_dtype", None),
+                max_grad_norm=self.max_grad_norm,
                 log=self.log)
             # seed fp32 master from current (averaged) params
             self.opt.init_master_from_buffer(self._params)
@@ -307,6 +311,11 @@ class DecoupledTrainer:
         loss = float(self.engine.loss_static.item()) if self.engine else 0.0
         self.scalars.log_training(round_idx // 2, count_grad_tot, self.rank,
                                   loss, eval_loss, self.t_beg)
+        com_log = self.engine.com_log if self.engine else []
+        if com_log and "grad_norm" in com_log[-1]:
+            # the last finished com round's norm, read by that round already
+            self.scalars.add_scalar(f"grad_norm/{self.rank}",
+                                    com_log[-1]["grad_norm"], round_idx)
         self.epoch, self.t_last_epoch = print_training_evolution(
             self.log, count_grad_tot, round_idx, 10, self.rank, self.t_beg,
             self.t_last_epoch, loss, self.epoch)
@@ -398,6 +407,11 @@ class DecoupledTrainer:
                 self.scalars.log_training(count_com, count_grad_tot,
                                           self.rank, loss_val, eval_loss,
                                           self.t_beg)
+                if self.opt.clipping:
+                    # next to the loss .item(): the step is synced already
+                    self.scalars.add_scalar(
+                        f"grad_norm/{self.rank}",
+                        float(self.opt.grad_norm.item()), count_com)
                 self.epoch, self.t_last_epoch = print_training_evolution(
                     self.log, count_grad_tot, count_com, 10, self.rank,
                     self.t_beg, self.t_last_epoch, loss_val, self.epoch)

@@ -235,6 +235,46 @@ def label_smoothed_causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,
 
 # ------------------------------------------------------------- trainer ops
 
+def grad_sumsq_partials(n: int, dtype: torch.dtype, device=None) -> int:
+    """Number of fp32 partials `grad_sumsq` writes for `n` elements of
+    `dtype` on `device` (default: the GPU when there is one): the kernel's
+    block count on the GPU, 1 for the CPU reference."""
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    if (torch.device(device).type != "cuda"
+            or os.environ.get("ACCO_FORCE_REF") == "1"):
+        return 1
+    return int(hip_ext().grad_sumsq_grid(int(n), dtype == torch.bfloat16))
+
+
+def grad_sumsq(g: torch.Tensor, partials: torch.Tensor) -> int:
+    """Sum of squares of a bf16 / fp32 gradient segment into fp32 partial
+    sums `partials[:count]`; returns count (= grad_sumsq_partials). Every
+    slot is stored, zero included, so the workspace needs no clearing; the
+    rest of `partials` is left alone. One streaming HIP kernel on GPU."""
+    if _use_ref(g):
+        return torch_ref.grad_sumsq(g, partials)
+    return int(hip_ext().grad_sumsq(g, partials))
+
+
+def sumsq_finalize(partials: torch.Tensor, out: torch.Tensor) -> None:
+    """out (1-element fp32) = sum of all of `partials`, in double, in a
+    fixed order. One single-block HIP kernel on GPU."""
+    if _use_ref(partials):
+        torch_ref.sumsq_finalize(partials, out)
+        return
+    hip_ext().sumsq_finalize(partials, out)
+
+
+def clip_grad_scale(sumsq: torch.Tensor, grad_scale, max_norm: float,
+                    eps: float = 1e-6):
+    """(scale, norm, coef) of global-norm clipping, clip_grad_norm_'s formula
+    folded into the AdamW gradient scale (torch_ref docstring). A few torch
+    ops on 1-element tensors on sumsq's device, no host sync: the scalar
+    all-reduce sits between the finalize kernel and this step."""
+    return torch_ref.clip_grad_scale(sumsq, grad_scale, max_norm, eps)
+
+
 def fused_adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                      v: torch.Tensor, step: int, lr: float, beta1: float,
                      beta2: float, eps: float, weight_decay: float,

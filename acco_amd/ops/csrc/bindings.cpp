@@ -81,6 +81,52 @@ void fused_adamw(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+// ---- gradient sum of squares (global grad-norm clipping)
+// The argument contract: g contiguous CUDA bf16 or fp32, 16-byte aligned
+// (16-byte vector loads); partials contiguous CUDA fp32 on g's device with
+// at least grad_sumsq_grid(n) elements. Returns the number of partials
+// written, partials[0 .. grid); the rest of the workspace is not touched.
+int64_t grad_sumsq_grid(int64_t n, bool is_bf16) {
+  TORCH_CHECK(n >= 0, "n must be >= 0, got ", n);
+  return acco_grad_sumsq_grid((long long)n, is_bf16);
+}
+
+int64_t grad_sumsq(at::Tensor g, at::Tensor partials) {
+  const bool bf16 = g.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(g.is_cuda() && (bf16 || g.scalar_type() == at::kFloat) &&
+              g.is_contiguous(), "g must be contiguous CUDA bf16 or fp32, "
+              "got ", g.scalar_type(), " on ", g.device());
+  TORCH_CHECK(aligned_to(g, 16), "g must be 16-byte aligned");
+  const int grid = acco_grad_sumsq_grid((long long)g.numel(), bf16);
+  TORCH_CHECK(partials.is_cuda() && partials.device() == g.device() &&
+              partials.scalar_type() == at::kFloat &&
+              partials.is_contiguous() && partials.numel() >= grid,
+              "partials must be contiguous CUDA fp32 with at least ", grid,
+              " elements on ", g.device(), ", got ", partials.scalar_type(),
+              " ", partials.sizes(), " on ", partials.device());
+  acco_grad_sumsq(g.data_ptr(), partials.data_ptr<float>(),
+                  (long long)g.numel(), bf16,
+                  at::hip::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return grid;
+}
+
+// out[0] = sum of every element of partials (double accumulation, fixed
+// order); partials contiguous CUDA fp32, out one fp32 on its device
+void sumsq_finalize(at::Tensor partials, at::Tensor out) {
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+              partials.is_contiguous(), "partials must be contiguous CUDA "
+              "fp32, got ", partials.scalar_type(), " on ", partials.device());
+  TORCH_CHECK(out.is_cuda() && out.device() == partials.device() &&
+              out.scalar_type() == at::kFloat && out.numel() == 1,
+              "out must be one fp32 on ", partials.device(), ", got ",
+              out.scalar_type(), " ", out.sizes(), " on ", out.device());
+  acco_sumsq_finalize(partials.data_ptr<float>(), (long long)partials.numel(),
+                      out.data_ptr<float>(),
+                      at::hip::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 at::Tensor colsum(at::Tensor in) {
   TORCH_CHECK(in.dim() == 2 && in.is_contiguous() && in.is_cuda());
   TORCH_CHECK(in.scalar_type() == at::kBFloat16 ||
@@ -891,6 +937,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adamw", &fused_adamw,
         "Fused sharded AdamW (gfx950): cast+scale+AdamW+bf16 writeout; "
         "commit=false = ACCO tentative step");
+  m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("partials"));
+  m.def("grad_sumsq_grid", &grad_sumsq_grid, py::arg("n"),
+        py::arg("is_bf16"));
+  m.def("sumsq_finalize", &sumsq_finalize, py::arg("partials"),
+        py::arg("out"));
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("swiglu_packed_fwd", &swiglu_packed_fwd);

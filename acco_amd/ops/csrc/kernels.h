@@ -17,6 +17,16 @@ void acco_fused_adamw_launch(void* p, const void* g, void* m, void* v,
                              float weight_decay, long long step_plus_1,
                              hipStream_t stream);
 
+// ---- gradnorm.hip
+// sum of squares of g[0..n) as acco_grad_sumsq_grid(n, is_bf16) fp32
+// partials (host only: the launch's block count; n = 0 gives one zero
+// partial); the finalize sums `count` partials in double into out[0]
+int acco_grad_sumsq_grid(long long n, bool is_bf16);
+void acco_grad_sumsq(const void* g, float* partials, long long n,
+                     bool is_bf16, hipStream_t stream);
+void acco_sumsq_finalize(const float* partials, long long count, float* out,
+                         hipStream_t stream);
+
 // ---- elementwise.hip
 void acco_swiglu_fwd(const void* g, const void* u, void* out, long long n,
                      int cols, long long row_stride8, hipStream_t s);

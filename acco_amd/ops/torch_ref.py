@@ -176,6 +176,40 @@ def label_smoothed_causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,
 
 
 @torch.no_grad()
+def grad_sumsq(g: torch.Tensor, partials: torch.Tensor) -> int:
+    """Sum of squares of a gradient segment as fp32 partial sums: the
+    reference writes one partial, slot 0, and returns the partial count."""
+    partials.view(-1)[0] = g.float().square().sum()
+    return 1
+
+
+@torch.no_grad()
+def sumsq_finalize(partials: torch.Tensor, out: torch.Tensor) -> None:
+    """out[0] = sum of the partials, accumulated in double."""
+    out.view(-1).copy_(partials.double().sum().float().reshape(1))
+
+
+@torch.no_grad()
+def clip_grad_scale(sumsq: torch.Tensor, grad_scale, max_norm: float,
+                    eps: float = 1e-6):
+    """Global-norm clipping folded into the gradient scale, the formula of
+    torch.nn.utils.clip_grad_norm_ on the gradient `grad_scale · g`:
+
+        norm  = sqrt(sumsq) · grad_scale
+        coef  = clamp(max_norm / (norm + eps), max=1)
+        scale = grad_scale · coef
+
+    sumsq: 1-element fp32 tensor holding sum(g²) of the unscaled gradient;
+    grad_scale: float or 1-element tensor (the engine's 1/count). Returns
+    1-element fp32 (scale, norm, coef) on sumsq's device; no host sync. A
+    non-finite norm propagates exactly as it does in torch."""
+    norm = (sumsq.float().sqrt() * grad_scale).float().reshape(1)
+    coef = torch.clamp(max_norm / (norm + eps), max=1.0)
+    scale = (coef * grad_scale).float().reshape(1)
+    return scale, norm, coef
+
+
+@torch.no_grad()
 def fused_adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
                      v: torch.Tensor, step: int, lr: float, beta1: float,
                      beta2: float, eps: float, weight_decay: float,

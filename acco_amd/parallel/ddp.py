@@ -137,12 +137,18 @@ class NativeZeroDDP:
     def finish_step(self, grad_scale: Union[float, torch.Tensor],
                     lr: Optional[float] = None) -> None:
         """After backward: drain per-bucket reduce-scatters (launching any
-        not yet launched), fused-AdamW each own segment, all-gather params."""
+        not yet launched), fused-AdamW each own segment, all-gather params.
+
+        With the optimizer's max_grad_norm set, the drain comes first as a
+        loop of its own with each bucket's sum of squares behind its
+        reduce-scatter, then one finalize with the scalar all-reduce (at
+        the same point on every rank), and the AdamW / all-gather loop runs
+        with the clipped scale."""
         self.sync_enabled = False
         if self.overlap:
             fuse_mod.set_grad_notifier(None)
-        ag = []
-        for b in range(self.spec.nb):
+
+        def drain(b: int) -> None:
             if self.overlap:
                 if not self._launched[b]:   # params with no grad this step
                     self._works[b] = self.comm.reduce_scatter_bucket_async(
@@ -151,6 +157,17 @@ class NativeZeroDDP:
             else:
                 self.comm.reduce_scatter_bucket_async(
                     self.grads, self.spec, b, self.rank).wait()
+
+        clipping = self.opt.clipping
+        if clipping:
+            for b in range(self.spec.nb):
+                drain(b)
+                self.opt.accumulate_sumsq(b, self.grads)
+            grad_scale = self.opt.finalize_clip(self.comm, grad_scale)
+        ag = []
+        for b in range(self.spec.nb):
+            if not clipping:
+                drain(b)
             # AdamW on own segment of the *grad* arena, emitting bf16 params
             # into the *params* arena segment (then gathered in place).
             gseg = self.spec.seg_view(self.grads, b, self.rank)

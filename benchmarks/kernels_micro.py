@@ -62,6 +62,11 @@ def main():
     report("adamw tentative (140M)", timeit(lambda: adamw(False), iters=10),
            n * (12 + 2 + 2))
 
+    # ---- gradient sum of squares (grad-norm clipping): read g bf16 only
+    part = torch.empty(ext.grad_sumsq_grid(n, True), device=DEV)
+    report("grad_sumsq (140M)",
+           timeit(lambda: ext.grad_sumsq(g, part), iters=10), n * 2)
+
     # ---- RMSNorm fwd/bwd (llama-1b: R=8192, D=2048)
     x = torch.randn(B, S, D, device=DEV, dtype=torch.bfloat16)
     w = torch.randn(D, device=DEV, dtype=torch.bfloat16)
