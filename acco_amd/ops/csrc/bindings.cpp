@@ -514,11 +514,15 @@ at::Tensor ce_bwd_dev(at::Tensor logits, at::Tensor labels, at::Tensor lse,
 }
 
 // ---- flash attention ([B, S, H, D] layout)
-struct AttnShape { int B, S, H, Hkv, D; };
+// window: what the kernels get, the caller's clamped to S (below)
+struct AttnShape { int B, S, H, Hkv, D, window; };
 
 // What every attention kernel needs of its sizes: D in {64, 128}, GQA groups
 // of whole heads, whole tiles (s_mult = 64, or 256 where only the 32x32
-// kernels are launched), window >= 0 and a 1-D grid that fits.
+// kernels are launched), window >= 0 and a 1-D grid that fits. A window >= S
+// bounds nothing, so it reaches the kernels as S: their int arithmetic on
+// row + window then stays below 2^31 (S < 2^30), and a 64-bit window is
+// never truncated to a small one by the cast.
 static AttnShape check_attn_dims(int64_t B, int64_t S, int64_t H, int64_t Hkv,
                                  int64_t D, int64_t window, int64_t s_mult) {
   TORCH_CHECK((D == 64 || D == 128) && H > 0 && Hkv > 0 && H % Hkv == 0,
@@ -530,7 +534,8 @@ static AttnShape check_attn_dims(int64_t B, int64_t S, int64_t H, int64_t Hkv,
   TORCH_CHECK(B > 0 && B * H <= 65535 && (S / 64) * B * H < (1LL << 31),
               "need 1 <= B*H <= 65535 and S/64 * B*H < 2^31 (the 1-D grid), "
               "got B=", B, " H=", H, " S=", S);
-  return {(int)B, (int)S, (int)H, (int)Hkv, (int)D};
+  return {(int)B, (int)S, (int)H, (int)Hkv, (int)D,
+          (int)(window < S ? window : S)};
 }
 
 // every tensor of `same` is contiguous bf16 on ref's device with ref's sizes
@@ -604,19 +609,19 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  double scale, int64_t window,
                                  c10::optional<at::Tensor> doc_start) {
   const AttnShape a = check_attn_args(q, k, v, window);
-  const auto [B, S, H, Hkv, D] = a;
+  const auto [B, S, H, Hkv, D, win] = a;
   const int* ds = check_attn_doc(q, a, doc_start, "doc_start", scale);
   auto o = at::empty_like(q);
   auto lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
   if (ds != nullptr) {
     acco_attn_fwd32(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                     lse.data_ptr<float>(), B, S, H, Hkv, D, (float)scale,
-                    (int)window, (long long)H * D, (long long)Hkv * D,
+                    win, (long long)H * D, (long long)Hkv * D,
                     (long long)H * D, ds, cur_stream());
   } else {
     acco_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                   lse.data_ptr<float>(), B, S, H, Hkv, D, (float)scale,
-                  (int)window, cur_stream());
+                  win, cur_stream());
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {o, lse};
@@ -643,7 +648,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  c10::optional<at::Tensor> doc_start,
                                  c10::optional<at::Tensor> doc_end) {
   const AttnShape a = check_attn_args(q, k, v, window, {dO}, {lse, delta});
-  const auto [B, S, H, Hkv, D] = a;
+  const auto [B, S, H, Hkv, D, win] = a;
   TORCH_CHECK(doc_start.has_value() == doc_end.has_value(),
               "doc_start and doc_end must both be given or both be None");
   const int* ds = check_attn_doc(q, a, doc_start, "doc_start", scale);
@@ -657,26 +662,26 @@ std::vector<at::Tensor> attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
     acco_attn_bwd32_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                        dO.data_ptr(), lse.data_ptr<float>(),
                        delta.data_ptr<float>(), dq.data_ptr(), B, S, H, Hkv,
-                       D, (float)scale, (int)window, qr, kr, qr, qr, nullptr,
+                       D, (float)scale, win, qr, kr, qr, qr, nullptr,
                        nullptr, ds, cur_stream());
     C10_HIP_KERNEL_LAUNCH_CHECK();
     acco_attn_bwd32_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                         dO.data_ptr(), lse.data_ptr<float>(),
                         delta.data_ptr<float>(), dk.data_ptr(), dv.data_ptr(),
-                        B, S, H, Hkv, D, (float)scale, (int)window, qr, kr,
+                        B, S, H, Hkv, D, (float)scale, win, qr, kr,
                         qr, de, cur_stream());
     C10_HIP_KERNEL_LAUNCH_CHECK();
     return {dq, dk, dv};
   }
   acco_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(), dO.data_ptr(),
                    lse.data_ptr<float>(), delta.data_ptr<float>(),
-                   dq.data_ptr(), B, S, H, Hkv, D, (float)scale, (int)window,
+                   dq.data_ptr(), B, S, H, Hkv, D, (float)scale, win,
                    cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   acco_attn_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), dO.data_ptr(),
                     lse.data_ptr<float>(), delta.data_ptr<float>(),
                     dk.data_ptr(), dv.data_ptr(), B, S, H, Hkv, D,
-                    (float)scale, (int)window, cur_stream());
+                    (float)scale, win, cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dq, dk, dv};
 }
@@ -871,7 +876,7 @@ std::vector<at::Tensor> attn_fwd_packed(at::Tensor qkv, int64_t H,
   auto lse = at::empty({a.B, a.H, a.S}, qkv.options().dtype(at::kFloat));
   acco_attn_fwd32(base + q_off, base + k_off, base + v_off, o.data_ptr(),
                   lse.data_ptr<float>(), a.B, a.S, a.H, a.Hkv, a.D,
-                  (float)scale, (int)window, W, W, H * D, ds, cur_stream());
+                  (float)scale, a.window, W, W, H * D, ds, cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {o, lse};
 }
@@ -918,14 +923,14 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
   acco_attn_bwd32_dq(base + q_off, base + k_off, base + v_off, dO.data_ptr(),
                      lse.data_ptr<float>(), delta.data_ptr<float>(),
                      dbase + q_off, B, S, (int)H, (int)Hkv, (int)D,
-                     (float)scale, (int)window, W, W, H * D, W, rc, rs, ds,
+                     (float)scale, a.window, W, W, H * D, W, rc, rs, ds,
                      cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   acco_attn_bwd32_dkv(base + q_off, base + k_off, base + v_off,
                       dO.data_ptr(), lse.data_ptr<float>(),
                       delta.data_ptr<float>(), dkq.data_ptr(),
                       dvq.data_ptr(), B, S, (int)H, (int)Hkv, (int)D,
-                      (float)scale, (int)window, W, W, H * D, de,
+                      (float)scale, a.window, W, W, H * D, de,
                       cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dkq, dvq};
