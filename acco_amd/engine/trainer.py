@@ -92,6 +92,12 @@ class DecoupledTrainer:
             if inner is not None:
                 inner.gradient_checkpointing = True
 
+        # chunked lm_head + loss: no [B, S, V] logits or dlogits
+        if getattr(args, "fused_lm_loss", False):
+            model.fused_lm_loss = True
+            model.lm_loss_chunk_tokens = int(
+                getattr(args, "lm_loss_chunk_tokens", 4096) or 4096)
+
         # ---- observability
         out_dir = os.getcwd()
         self.scalars = ScalarLogger(os.path.join(out_dir, "scalars"),
@@ -260,7 +266,14 @@ class DecoupledTrainer:
         DDP mode — ACCO averages by global grad count instead)"""
         ls = float(getattr(self.args, "label_smoothing_factor", 0) or 0)
         with self._autocast():
-            if ls != 0.0:
+            if ls != 0.0 and getattr(self.model, "fused_lm_loss", False):
+                # the model's chunked head smooths inside its row kernels;
+                # asking it for logits would materialise them
+                labels = inputs.get("labels", inputs["input_ids"])
+                extra = {k: v for k, v in inputs.items() if k != "labels"}
+                loss = self.model(**extra, labels=labels,
+                                  label_smoothing=ls)[0] / self.loss_div
+            elif ls != 0.0:
                 # label-smoothed path (reference compute_loss :262-282 with
                 # LabelSmoother): loss computed outside the model head —
                 # fused into the CE HIP kernel on GPU (K9)

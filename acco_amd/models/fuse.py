@@ -52,11 +52,15 @@ def _notify(g_view) -> None:
         _grad_notifier(g_view.storage_offset(), g_view.numel())
 
 
-def _acc_wgrad(g_view, d2t, x2):
+def _add_wgrad(g_view, d2t, x2):
     if _EPILOGUE:
         g_view.addmm_(d2t, x2)
     else:
         g_view.add_(torch.matmul(d2t, x2))
+
+
+def _acc_wgrad(g_view, d2t, x2):
+    _add_wgrad(g_view, d2t, x2)
     _notify(g_view)
 
 
@@ -126,6 +130,25 @@ def arena_linear(lin: nn.Linear, x: torch.Tensor) -> torch.Tensor:
         return lin(x)
     w_view, g_w, b, g_b = fuse
     return ArenaLinearFn.apply(x, w_view, b, g_w, g_b)
+
+
+def arena_lm_loss(lin: nn.Linear, hidden: torch.Tensor, labels: torch.Tensor,
+                  epsilon: float = 0.0,
+                  chunk_tokens: int = 4096) -> torch.Tensor:
+    """Shifted causal-LM loss of the bias-free head `lin` on `hidden` without
+    the [B, S, V] logits (ops.linear_causal_lm_loss): dW accumulates in place
+    into the grad arena if `install_fused_projections` wrapped `lin`, and
+    comes back through autograd on `lin.weight` otherwise."""
+    from acco_amd import ops
+    if lin.bias is not None:
+        raise RuntimeError("arena_lm_loss needs a bias-free lm_head")
+    fuse = getattr(lin, "_arena_fuse", None)
+    if fuse is None:
+        return ops.linear_causal_lm_loss(hidden, lin.weight, labels, epsilon,
+                                         chunk_tokens)
+    w_view, g_w, _b, _g_b = fuse
+    return ops.linear_causal_lm_loss(hidden, w_view, labels, epsilon,
+                                     chunk_tokens, grad_view=g_w)
 
 
 def _arena_views(params: List[nn.Parameter], arena: torch.Tensor,

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from acco_amd import ops
-from acco_amd.models.fuse import arena_linear
+from acco_amd.models.fuse import arena_linear, arena_lm_loss
 from acco_amd.models.config import GPTNeoConfig
 
 
@@ -159,6 +159,10 @@ class GPTNeoModel(nn.Module):
 
 class GPTNeoForCausalLM(nn.Module):
     config_class = GPTNeoConfig
+    # train.fused_lm_loss / train.lm_loss_chunk_tokens (LlamaForCausalLM has
+    # the note)
+    fused_lm_loss = False
+    lm_loss_chunk_tokens = 4096
 
     def __init__(self, cfg: GPTNeoConfig):
         super().__init__()
@@ -184,14 +188,23 @@ class GPTNeoForCausalLM(nn.Module):
     def forward(self, input_ids: torch.Tensor,
                 labels: Optional[torch.Tensor] = None,
                 attention_mask: Optional[torch.Tensor] = None,
-                doc_start: Optional[torch.Tensor] = None):
+                doc_start: Optional[torch.Tensor] = None,
+                label_smoothing: float = 0.0):
         """`attention_mask` is accepted and unused; `doc_start` (int32
         [B, S], ops.doc_start_from_eos) keeps attention inside each document
-        of a packed row and restarts the positions per document."""
+        of a packed row and restarts the positions per document.
+        `label_smoothing` is the HF-LabelSmoother epsilon of the loss. With
+        `fused_lm_loss` set and labels given the result is (loss, None)."""
         hidden = (self.transformer(input_ids) if doc_start is None
                   else self.transformer(input_ids, doc_start))
+        if labels is not None and self.fused_lm_loss:
+            # chunked head + loss: the [B, S, V] logits never exist
+            loss = arena_lm_loss(self.lm_head, hidden, labels,
+                                 label_smoothing, self.lm_loss_chunk_tokens)
+            return (loss, None)
         logits = arena_linear(self.lm_head, hidden)
         if labels is None:
             return (logits,)
-        loss = ops.causal_lm_loss(logits, labels)
+        loss = ops.label_smoothed_causal_lm_loss(logits, labels,
+                                                 label_smoothing)
         return (loss, logits)

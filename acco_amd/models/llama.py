@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from acco_amd import ops
 from acco_amd.models.config import LlamaConfig
-from acco_amd.models.fuse import arena_linear
+from acco_amd.models.fuse import arena_linear, arena_lm_loss
 
 
 class LlamaRMSNorm(nn.Module):
@@ -195,6 +195,12 @@ class LlamaModel(nn.Module):
 
 class LlamaForCausalLM(nn.Module):
     config_class = LlamaConfig
+    # train.fused_lm_loss: with labels, compute the loss through the chunked
+    # head (fuse.arena_lm_loss) and return (loss, None). 4096 rows bound the
+    # logits buffer at 1 GB for V = 128k; which chunk size is fastest has not
+    # been measured.
+    fused_lm_loss = False
+    lm_loss_chunk_tokens = 4096
 
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -217,16 +223,25 @@ class LlamaForCausalLM(nn.Module):
     def forward(self, input_ids: torch.Tensor,
                 labels: Optional[torch.Tensor] = None,
                 attention_mask: Optional[torch.Tensor] = None,
-                doc_start: Optional[torch.Tensor] = None):
+                doc_start: Optional[torch.Tensor] = None,
+                label_smoothing: float = 0.0):
         """HF-compatible call: returns (loss, logits) when labels given,
         (logits,) otherwise — the trainer indexes outputs[0]
         (reference trainer_decoupled.py:29-34). `attention_mask` is accepted
         and unused. `doc_start` (int32 [B, S], ops.doc_start_from_eos) keeps
-        attention inside each document of a packed row."""
+        attention inside each document of a packed row. `label_smoothing`
+        is the HF-LabelSmoother epsilon of the loss. With `fused_lm_loss`
+        set and labels given the result is (loss, None)."""
         hidden = (self.model(input_ids) if doc_start is None
                   else self.model(input_ids, doc_start))
+        if labels is not None and self.fused_lm_loss:
+            # chunked head + loss: the [B, S, V] logits never exist
+            loss = arena_lm_loss(self.lm_head, hidden, labels,
+                                 label_smoothing, self.lm_loss_chunk_tokens)
+            return (loss, None)
         logits = arena_linear(self.lm_head, hidden)
         if labels is None:
             return (logits,)
-        loss = ops.causal_lm_loss(logits, labels)
+        loss = ops.label_smoothed_causal_lm_loss(logits, labels,
+                                                 label_smoothing)
         return (loss, logits)

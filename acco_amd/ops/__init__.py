@@ -233,6 +233,52 @@ def label_smoothed_causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,
     return CausalLMLossFn.apply(logits, labels, epsilon)
 
 
+def linear_causal_lm_loss(hidden: torch.Tensor, weight: torch.Tensor,
+                          labels: torch.Tensor, epsilon: float = 0.0,
+                          chunk_tokens: int = 4096,
+                          grad_view: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
+    """lm_head + shifted causal-LM loss without the [B, S, V] logits: the
+    scalar mean loss of `hidden @ weight^T` (hidden [B, S, H], weight [V, H],
+    no bias) against labels [B, S] over the valid shifted tokens (a label is
+    valid iff 0 <= label < V), with HF-LabelSmoother smoothing for
+    epsilon != 0. Logits exist for `chunk_tokens` rows at a time, in one
+    reused buffer of chunk_tokens·V elements; the backward recomputes them
+    (one extra head GEMM per step) and overwrites them with dlogits in
+    place. The loss is summed in a fixed order: bitwise reproducible.
+
+    With `grad_view` (the grad-arena view aliasing `weight`) dW accumulates
+    into it in place, one chunk at a time, the producer notifier fires once
+    after the last chunk and no weight gradient is returned; without it the
+    chunks accumulate in fp32 and dW comes back cast once.
+
+    On the GPU: bf16 contiguous hidden and weight, row kernels of
+    ce_rows.hip. CPU tensors and ACCO_FORCE_REF=1 run the same chunking in
+    torch math."""
+    if _use_ref(hidden):
+        return torch_ref.linear_causal_lm_loss(hidden, weight, labels,
+                                               epsilon, chunk_tokens,
+                                               grad_view)
+    hip_ext()   # a missing extension is an error, not a fallback
+    if int(chunk_tokens) < 1:
+        raise ValueError(f"chunk_tokens must be >= 1, got {chunk_tokens}")
+    if not (hidden.dtype == weight.dtype == torch.bfloat16
+            and hidden.is_contiguous() and weight.is_contiguous()
+            and hidden.dim() == 3 and weight.dim() == 2
+            and weight.shape[1] == hidden.shape[2]):
+        raise RuntimeError(
+            "linear_causal_lm_loss on the GPU needs contiguous bf16 hidden "
+            f"[B, S, H] and weight [V, H], got {hidden.dtype} "
+            f"{tuple(hidden.shape)} (contiguous={hidden.is_contiguous()}) and "
+            f"{weight.dtype} {tuple(weight.shape)} "
+            f"(contiguous={weight.is_contiguous()})")
+    from acco_amd.ops.autograd import LinearCausalLMLossFn
+    targets, n_valid = torch_ref.shifted_targets(labels, weight.shape[0])
+    return LinearCausalLMLossFn.apply(
+        hidden.view(-1, hidden.shape[-1]), weight, targets, n_valid,
+        float(epsilon), int(chunk_tokens), grad_view)
+
+
 # ------------------------------------------------------------- trainer ops
 
 def grad_sumsq_partials(n: int, dtype: torch.dtype, device=None) -> int:

@@ -186,6 +186,49 @@ class CausalLMLossFn(torch.autograd.Function):
         return dlogits, None, None
 
 
+class HipRows:
+    """Row kernels of the chunked lm_head + loss (ce_rows.hip): per-row lse
+    and loss in fp32, dlogits in place, the loss summed in double in a fixed
+    order by the finalize kernel."""
+
+    @staticmethod
+    def stat_dtype(dtype):
+        return torch.float32
+
+    @staticmethod
+    def fwd(lg, tg, lse, tok, eps):
+        ops.hip_ext().ce_rows_fwd(lg, tg, lse, tok, eps)
+
+    @staticmethod
+    def bwd_(lg, tg, lse, scale, eps):
+        ops.hip_ext().ce_rows_bwd_(lg, tg, lse, scale, eps)
+
+    @staticmethod
+    def total(tok):
+        out = torch.empty(1, dtype=torch.float32, device=tok.device)
+        ops.hip_ext().sumsq_finalize(tok, out)
+        return out
+
+
+class LinearCausalLMLossFn(torch.autograd.Function):
+    """lm_head GEMM + shifted CE, `chunk_tokens` rows of logits at a time
+    (torch_ref.chunked_lm_loss_forward / _backward hold the chunk loop):
+    hidden2 [T, H] and weight [V, H] bf16 contiguous, targets int64 [T]
+    already shifted, n_valid a device scalar. Saves no logits."""
+
+    @staticmethod
+    def forward(ctx, hidden2, weight, targets, n_valid, epsilon, chunk_tokens,
+                grad_view):
+        return ops.torch_ref.chunked_lm_loss_forward(
+            ctx, HipRows, hidden2, weight, targets, n_valid, epsilon,
+            chunk_tokens, grad_view)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dh, dw = ops.torch_ref.chunked_lm_loss_backward(ctx, grad_out)
+        return dh, dw, None, None, None, None, None
+
+
 class AttnQKVPackedFn(torch.autograd.Function):
     """The whole attention core over the PACKED fused projection output
     [B, S, (H+2Hkv)·D]: optional RoPE + flash attention v4 forward; backward

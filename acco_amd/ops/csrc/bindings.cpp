@@ -513,6 +513,79 @@ at::Tensor ce_bwd_dev(at::Tensor logits, at::Tensor labels, at::Tensor lse,
   return dlogits;
 }
 
+// ---- row-wise CE of the chunked lm_head + loss path
+struct CeRowsShape { long long T; int V; };
+
+// The argument contract of the row-wise CE entry points: logits contiguous
+// CUDA bf16 [T, V] on a 16-byte aligned base, 0 < V < 2^31; targets
+// contiguous int64 with T elements on the logits' device (already shifted:
+// targets[t] is the label of row t); lse and tok_loss contiguous fp32 with T
+// elements on that device; in the backward, scale_dev one fp32 there.
+static CeRowsShape check_ce_rows_args(const at::Tensor& logits,
+                                      const at::Tensor& targets,
+                                      const at::Tensor& lse,
+                                      const at::Tensor* tok_loss,
+                                      const at::Tensor* scale_dev) {
+  CHECK_BF16_CONTIG(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) > 0 &&
+              logits.size(1) < (1LL << 31),
+              "logits must be [T, V] with 0 < V < 2^31, got ", logits.sizes());
+  TORCH_CHECK(aligned_to(logits, 16), "logits must be 16-byte aligned");
+  const int64_t T = logits.size(0);
+  TORCH_CHECK(targets.is_cuda() && targets.device() == logits.device() &&
+              targets.scalar_type() == at::kLong && targets.is_contiguous() &&
+              targets.numel() == T, "targets must be contiguous int64 with T"
+              " = ", T, " elements on ", logits.device(), ", got ",
+              targets.scalar_type(), " ", targets.sizes(), " on ",
+              targets.device());
+  auto check_rowvec = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == logits.device() &&
+                t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                t.numel() == T, name, " must be contiguous CUDA fp32 with T"
+                " = ", T, " elements on ", logits.device(), ", got ",
+                t.scalar_type(), " ", t.sizes(), " on ", t.device());
+  };
+  check_rowvec(lse, "lse");
+  if (tok_loss != nullptr) check_rowvec(*tok_loss, "tok_loss");
+  if (scale_dev != nullptr)
+    TORCH_CHECK(scale_dev->is_cuda() &&
+                scale_dev->device() == logits.device() &&
+                scale_dev->scalar_type() == at::kFloat &&
+                scale_dev->numel() == 1, "scale_dev must be one fp32 on ",
+                logits.device(), ", got ", scale_dev->scalar_type(), " ",
+                scale_dev->sizes(), " on ", scale_dev->device());
+  return {(long long)T, (int)logits.size(1)};
+}
+
+// lse[t], tok_loss[t] of every row (0 on ignored rows), stored into the
+// caller's buffers
+void ce_rows_fwd(at::Tensor logits, at::Tensor targets, at::Tensor lse,
+                 at::Tensor tok_loss, double epsilon) {
+  const auto [T, V] = check_ce_rows_args(logits, targets, lse, &tok_loss,
+                                         nullptr);
+  if (T == 0) return;
+  acco_ce_rows_fwd(logits.data_ptr(),
+                   reinterpret_cast<const long long*>(
+                       targets.data_ptr<int64_t>()),
+                   lse.data_ptr<float>(), tok_loss.data_ptr<float>(), T, V,
+                   (float)epsilon, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// logits become scale_dev[0] · dloss/dlogits in place
+void ce_rows_bwd_(at::Tensor logits, at::Tensor targets, at::Tensor lse,
+                  at::Tensor scale_dev, double epsilon) {
+  const auto [T, V] = check_ce_rows_args(logits, targets, lse, nullptr,
+                                         &scale_dev);
+  if (T == 0) return;
+  acco_ce_rows_bwd(logits.data_ptr(),
+                   reinterpret_cast<const long long*>(
+                       targets.data_ptr<int64_t>()),
+                   lse.data_ptr<float>(), scale_dev.data_ptr<float>(), T, V,
+                   (float)epsilon, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 // ---- flash attention ([B, S, H, D] layout)
 // window: what the kernels get, the caller's clamped to S (below)
 struct AttnShape { int B, S, H, Hkv, D, window; };
@@ -972,6 +1045,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd_dev", &ce_bwd_dev, py::arg("logits"), py::arg("labels"),
         py::arg("lse"), py::arg("acc"), py::arg("dloss_dev"),
         py::arg("epsilon") = 0.0);
+  m.def("ce_rows_fwd", &ce_rows_fwd, py::arg("logits"), py::arg("targets"),
+        py::arg("lse"), py::arg("tok_loss"), py::arg("epsilon") = 0.0);
+  m.def("ce_rows_bwd_", &ce_rows_bwd_, py::arg("logits"), py::arg("targets"),
+        py::arg("lse"), py::arg("scale_dev"), py::arg("epsilon") = 0.0);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("scale"), py::arg("window"),
         py::arg("doc_start") = py::none());

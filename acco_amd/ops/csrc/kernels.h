@@ -77,6 +77,18 @@ void acco_ce_bwd(const void* logits, const long long* labels,
                  float dloss, const float* dloss_dev, long long T, int S,
                  int V, float epsilon, hipStream_t s);
 
+// ---- ce_rows.hip
+// bf16 rows [T, V] on a 16-byte aligned base (any V), targets[t] the label
+// of row t (valid iff 0 <= target < V); fwd stores lse[t] and tok_loss[t]
+// for every t (0 on ignored rows), bwd overwrites the rows with dlogits
+// scaled by the device scalar *scale_dev
+void acco_ce_rows_fwd(const void* logits, const long long* targets,
+                      float* lse, float* tok_loss, long long T, int V,
+                      float epsilon, hipStream_t s);
+void acco_ce_rows_bwd(void* logits_inout, const long long* targets,
+                      const float* lse, const float* scale_dev, long long T,
+                      int V, float epsilon, hipStream_t s);
+
 // ---- gemm_nt.hip
 void acco_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K,
                   hipStream_t stream);

@@ -175,6 +175,152 @@ def label_smoothed_causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,
     return (1.0 - epsilon) * nll + epsilon * smooth
 
 
+# ------------------------------------------- chunked lm_head + shifted CE
+# The [B, S, V] logits are never materialised: a chunk of `chunk_tokens` rows
+# is projected into one reused [C, V] buffer, reduced to per-row lse and loss,
+# and dropped; the backward recomputes the chunk, turns the buffer into
+# dlogits in place and feeds the dh and dW GEMMs from it. The chunk loop below
+# is shared by the torch-math path (here) and the HIP path (ops/autograd.py),
+# which differ in the row kernels only.
+
+def shifted_targets(labels: torch.Tensor, V: int):
+    """(targets int64 [B·S], n_valid 0-dim int64): targets[b·S + s] =
+    labels[b, s + 1], -100 at each row's last position; a target is valid iff
+    0 <= target < V. Plain torch ops on the labels' device, no host sync."""
+    labels = labels.long()
+    targets = torch.full_like(labels, -100)
+    targets[..., :-1] = labels[..., 1:]
+    targets = targets.reshape(-1)
+    n_valid = ((targets >= 0) & (targets < V)).sum()
+    return targets, n_valid
+
+
+class TorchRows:
+    """Row kernels of the chunked loss in torch math, in the wider of the
+    logits' dtype and fp32."""
+
+    @staticmethod
+    def stat_dtype(dtype: torch.dtype) -> torch.dtype:
+        return torch.promote_types(dtype, torch.float32)
+
+    @staticmethod
+    def fwd(lg, tg, lse, tok, eps):
+        V = lg.shape[1]
+        x = lg.to(lse.dtype)
+        valid = (tg >= 0) & (tg < V)
+        l = torch.logsumexp(x, dim=-1)
+        t = l - x.gather(1, tg.clamp(0, V - 1)[:, None]).squeeze(1)
+        if eps != 0.0:
+            t = (1.0 - eps) * t + eps * (l - x.sum(-1) / V)
+        zero = torch.zeros_like(l)
+        lse.copy_(torch.where(valid, l, zero))
+        tok.copy_(torch.where(valid, t, zero))
+
+    @staticmethod
+    def bwd_(lg, tg, lse, scale, eps):
+        V = lg.shape[1]
+        x = lg.to(lse.dtype)
+        valid = (tg >= 0) & (tg < V)
+        p = torch.exp(x - lse[:, None]) - eps / V
+        p.scatter_add_(1, tg.clamp(0, V - 1)[:, None],
+                       torch.full_like(p[:, :1], -(1.0 - eps)))
+        lg.copy_(torch.where(valid[:, None], p * scale, torch.zeros_like(p)))
+
+    @staticmethod
+    def total(tok):
+        return tok.double().sum().to(tok.dtype).reshape(1)
+
+
+def chunked_lm_loss_forward(ctx, rows, hidden2, weight, targets, n_valid,
+                            epsilon, chunk_tokens, grad_view):
+    """hidden2 [T, H], weight [V, H], targets [T] (already shifted). Saves
+    hidden, weight, targets, lse and the denominator; never the logits."""
+    T, V = hidden2.shape[0], weight.shape[0]
+    C = max(1, min(int(chunk_tokens), T))
+    sdt = rows.stat_dtype(hidden2.dtype)
+    buf = hidden2.new_empty((C, V))
+    lse = torch.empty(T, dtype=sdt, device=hidden2.device)
+    tok = torch.empty_like(lse)
+    for s in range(0, T, C):
+        e = min(s + C, T)
+        lg = buf[:e - s]
+        torch.mm(hidden2[s:e], weight.t(), out=lg)
+        rows.fwd(lg, targets[s:e], lse[s:e], tok[s:e], epsilon)
+    denom = n_valid.clamp(min=1).to(sdt)
+    ctx.save_for_backward(hidden2, weight, targets, lse, denom)
+    ctx.meta = (rows, float(epsilon), C, grad_view)
+    # one fixed-order sum over all rows: bitwise reproducible
+    return (rows.total(tok) / denom).reshape(())
+
+
+def chunked_lm_loss_backward(ctx, grad_out):
+    """(dh, dW): dW is None when it went into the grad-arena view. The
+    upstream gradient is applied here (the trainer divides the loss), as a
+    device scalar: no host read."""
+    from acco_amd.models import fuse
+    hidden2, weight, targets, lse, denom = ctx.saved_tensors
+    rows, eps, C, g_view = ctx.meta
+    T, V = hidden2.shape[0], weight.shape[0]
+    scale = grad_out.to(lse.dtype).reshape(1) / denom
+    buf = hidden2.new_empty((C, V))
+    dh = torch.empty_like(hidden2)
+    dw = None
+    if g_view is None and ctx.needs_input_grad[1]:
+        dw = torch.zeros(weight.shape, device=weight.device,
+                         dtype=torch.promote_types(weight.dtype,
+                                                   torch.float32))
+    for s in range(0, T, C):
+        e = min(s + C, T)
+        lg, h = buf[:e - s], hidden2[s:e]
+        torch.mm(h, weight.t(), out=lg)
+        rows.bwd_(lg, targets[s:e], lse[s:e], scale, eps)
+        torch.mm(lg, weight, out=dh[s:e])
+        if g_view is not None:
+            fuse._add_wgrad(g_view, lg.t(), h)
+        elif dw is not None and lg.is_cuda and lg.dtype != dw.dtype:
+            # fp32 out of the bf16 GEMM: no wide copy of the chunk
+            dw.add_(torch.mm(lg.t(), h, out_dtype=dw.dtype))
+        elif dw is not None:
+            dw.addmm_(lg.t().to(dw.dtype), h.to(dw.dtype))
+    if g_view is not None:
+        # once, after the last chunk: the DDP tracker counts covered elements
+        # per notification
+        fuse._notify(g_view)
+    return dh, (dw.to(weight.dtype) if dw is not None else None)
+
+
+class LinearCausalLMLossRefFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden2, weight, targets, n_valid, epsilon, chunk_tokens,
+                grad_view):
+        return chunked_lm_loss_forward(ctx, TorchRows, hidden2, weight,
+                                       targets, n_valid, epsilon,
+                                       chunk_tokens, grad_view)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dh, dw = chunked_lm_loss_backward(ctx, grad_out)
+        return dh, dw, None, None, None, None, None
+
+
+def linear_causal_lm_loss(hidden: torch.Tensor, weight: torch.Tensor,
+                          labels: torch.Tensor, epsilon: float = 0.0,
+                          chunk_tokens: int = 4096,
+                          grad_view: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
+    """Mean shifted causal-LM loss of `hidden @ weight^T` over the valid
+    tokens (label smoothing as label_smoothed_causal_lm_loss), `chunk_tokens`
+    rows of logits at a time. hidden [B, S, H], weight [V, H], labels [B, S].
+    With `grad_view` the weight gradient is accumulated into it in place and
+    none is returned."""
+    if int(chunk_tokens) < 1:
+        raise ValueError(f"chunk_tokens must be >= 1, got {chunk_tokens}")
+    targets, n_valid = shifted_targets(labels, weight.shape[0])
+    return LinearCausalLMLossRefFn.apply(
+        hidden.reshape(-1, hidden.shape[-1]), weight, targets, n_valid,
+        float(epsilon), int(chunk_tokens), grad_view)
+
+
 @torch.no_grad()
 def grad_sumsq(g: torch.Tensor, partials: torch.Tensor) -> int:
     """Sum of squares of a gradient segment as fp32 partial sums: the

@@ -58,6 +58,11 @@ def main(argv=None):
         sd = torch.load(ckpt, map_location="cpu", weights_only=True)
         model.load_state_dict(sd)
     model = model.to(device, dtype=dtype)
+    # train.fused_lm_loss: long eval rows are where full logits cost most
+    if cfg.train.get("fused_lm_loss", False):
+        model.fused_lm_loss = True
+        model.lm_loss_chunk_tokens = int(
+            cfg.train.get("lm_loss_chunk_tokens", 4096) or 4096)
 
     tok = None
     if cfg.data.get("kind") == "synthetic":
