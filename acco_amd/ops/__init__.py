@@ -253,7 +253,7 @@ def linear_causal_lm_loss(hidden: torch.Tensor, weight: torch.Tensor,
     chunks accumulate in fp32 and dW comes back cast once.
 
     On the GPU: bf16 contiguous hidden and weight, row kernels of
-    ce_rows.hip. CPU tensors and ACCO_FORCE_REF=1 run the same chunking in
+    ce.hip. CPU tensors and ACCO_FORCE_REF=1 run the same chunking in
     torch math."""
     if _use_ref(hidden):
         return torch_ref.linear_causal_lm_loss(hidden, weight, labels,

@@ -165,6 +165,10 @@ class CausalLMLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, epsilon=0.0):
         logits = logits.contiguous()
+        if logits.data_ptr() % 16 != 0:
+            # the kernels load 16-byte vectors from a 16-byte aligned base;
+            # GEMM outputs are, an offset view into a larger buffer may not be
+            logits = logits.clone()
         labels = labels.contiguous()
         acc, lse = ops.hip_ext().ce_fwd(logits, labels, float(epsilon))
         ctx.save_for_backward(logits, labels, lse, acc)
@@ -174,22 +178,18 @@ class CausalLMLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         logits, labels, lse, acc = ctx.saved_tensors
-        ext = ops.hip_ext()
-        if grad_out.is_cuda and hasattr(ext, "ce_bwd_dev"):
-            # read the upstream grad on-device — float(grad_out) would be a
-            # D2H sync stalling the backward launch pipeline every micro
-            dlogits = ext.ce_bwd_dev(logits, labels, lse, acc,
-                                     grad_out.reshape(1).float(), ctx.epsilon)
-        else:
-            dlogits = ext.ce_bwd(logits, labels, lse, acc, float(grad_out),
-                                 ctx.epsilon)
+        # the upstream grad is read on-device — float(grad_out) would be a
+        # D2H sync stalling the backward launch pipeline every micro
+        dlogits = ops.hip_ext().ce_bwd_dev(
+            logits, labels, lse, acc,
+            grad_out.reshape(1).to(logits.device, torch.float32), ctx.epsilon)
         return dlogits, None, None
 
 
 class HipRows:
-    """Row kernels of the chunked lm_head + loss (ce_rows.hip): per-row lse
-    and loss in fp32, dlogits in place, the loss summed in double in a fixed
-    order by the finalize kernel."""
+    """Row kernels of the chunked lm_head + loss (ce.hip, Rows policy):
+    per-row lse and loss in fp32, dlogits in place, the loss summed in
+    double in a fixed order by the finalize kernel."""
 
     @staticmethod
     def stat_dtype(dtype):

@@ -18,6 +18,25 @@ static bool aligned_to(const at::Tensor& t, size_t bytes) {
   return reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0;
 }
 
+// one fp32 element on ref's device
+static void check_dev_scalar(const at::Tensor& t, const at::Tensor& ref,
+                             const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device() &&
+              t.scalar_type() == at::kFloat && t.numel() == 1, name,
+              " must be one fp32 on ", ref.device(), ", got ",
+              t.scalar_type(), " ", t.sizes(), " on ", t.device());
+}
+
+// contiguous CUDA fp32 with n elements on ref's device
+static void check_f32_vec(const at::Tensor& t, int64_t n,
+                          const at::Tensor& ref, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device() &&
+              t.scalar_type() == at::kFloat && t.is_contiguous() &&
+              t.numel() == n, name, " must be contiguous CUDA fp32 with ", n,
+              " elements on ", ref.device(), ", got ", t.scalar_type(), " ",
+              t.sizes(), " on ", t.device());
+}
+
 // The argument contract of the fused AdamW: p, m, v contiguous CUDA fp32 of
 // one numel on one device, 16-byte aligned (float4 accesses); g (and out,
 // when given) contiguous bf16 or fp32 of that numel on that device, aligned
@@ -64,11 +83,7 @@ void fused_adamw(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
   }
   const float* sd = nullptr;
   if (scale_dev.numel() > 0) {
-    TORCH_CHECK(scale_dev.scalar_type() == at::kFloat && scale_dev.is_cuda() &&
-                scale_dev.device() == p.device() && scale_dev.numel() == 1,
-                "scale_dev must be one fp32 on ", p.device(), ", got ",
-                scale_dev.scalar_type(), " ", scale_dev.sizes(), " on ",
-                scale_dev.device());
+    check_dev_scalar(scale_dev, p, "scale_dev");
     sd = scale_dev.data_ptr<float>();
   }
   if (p.numel() == 0) return;
@@ -117,10 +132,7 @@ void sumsq_finalize(at::Tensor partials, at::Tensor out) {
   TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
               partials.is_contiguous(), "partials must be contiguous CUDA "
               "fp32, got ", partials.scalar_type(), " on ", partials.device());
-  TORCH_CHECK(out.is_cuda() && out.device() == partials.device() &&
-              out.scalar_type() == at::kFloat && out.numel() == 1,
-              "out must be one fp32 on ", partials.device(), ", got ",
-              out.scalar_type(), " ", out.sizes(), " on ", out.device());
+  check_dev_scalar(out, partials, "out");
   acco_sumsq_finalize(partials.data_ptr<float>(), (long long)partials.numel(),
                       out.data_ptr<float>(),
                       at::hip::getCurrentHIPStream().stream());
@@ -429,13 +441,15 @@ at::Tensor rope_fwd(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t,
   return y;
 }
 
-// ---- fused shifted causal-LM CE
+// ---- fused causal-LM CE (ce.hip): whole [B, S, V] logits, labels shifted
+// by the kernels
 struct CeShape { long long T; int S, V; };
 
-// The argument contract of the CE entry points: logits contiguous CUDA bf16
-// [B, S, V]; labels contiguous int64 [B, S] on the logits' device; in the
-// backward, lse contiguous fp32 with one element per token and acc fp32
-// {loss_sum, n_valid, ...}, both on that device.
+// The argument contract of the shifted CE entry points: logits contiguous
+// CUDA bf16 [B, S, V] on a 16-byte aligned base; labels contiguous int64
+// [B, S] on the logits' device (a label outside [0, V) is an ignored token);
+// in the backward, lse contiguous fp32 with one element per token and acc
+// fp32 {loss_sum, n_valid, ...}, both on that device.
 static CeShape check_ce_args(const at::Tensor& logits,
                              const at::Tensor& labels,
                              const at::Tensor* lse = nullptr,
@@ -444,6 +458,7 @@ static CeShape check_ce_args(const at::Tensor& logits,
   TORCH_CHECK(logits.dim() == 3 && logits.size(1) < (1LL << 31) &&
               logits.size(2) > 0 && logits.size(2) < (1LL << 31),
               "logits must be [B,S,V] with V > 0, got ", logits.sizes());
+  TORCH_CHECK(aligned_to(logits, 16), "logits must be 16-byte aligned");
   const int64_t B = logits.size(0), S = logits.size(1);
   TORCH_CHECK(labels.is_cuda() && labels.device() == logits.device() &&
               labels.scalar_type() == at::kLong && labels.is_contiguous() &&
@@ -451,12 +466,7 @@ static CeShape check_ce_args(const at::Tensor& logits,
               "labels must be contiguous int64 [B, S] = [", B, ", ", S,
               "] on ", logits.device(), ", got ", labels.scalar_type(), " ",
               labels.sizes(), " on ", labels.device());
-  if (lse != nullptr)
-    TORCH_CHECK(lse->is_cuda() && lse->device() == logits.device() &&
-                lse->scalar_type() == at::kFloat && lse->is_contiguous() &&
-                lse->numel() == B * S, "lse must be contiguous CUDA fp32 with "
-                "B*S = ", B * S, " elements on ", logits.device(), ", got ",
-                lse->scalar_type(), " ", lse->sizes(), " on ", lse->device());
+  if (lse != nullptr) check_f32_vec(*lse, B * S, logits, "lse");
   if (acc != nullptr)
     TORCH_CHECK(acc->is_cuda() && acc->device() == logits.device() &&
                 acc->scalar_type() == at::kFloat && acc->is_contiguous() &&
@@ -481,39 +491,37 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor labels,
   return {accs.sum(0), lse};
 }
 
-at::Tensor ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor lse,
-                  at::Tensor acc, double dloss, double epsilon) {
+// dloss from the host, or from dloss_dev (one fp32 on the device) when given
+static at::Tensor ce_bwd_impl(const at::Tensor& logits,
+                              const at::Tensor& labels, const at::Tensor& lse,
+                              const at::Tensor& acc, double dloss,
+                              const at::Tensor* dloss_dev, double epsilon) {
   const auto [T, S, V] = check_ce_args(logits, labels, &lse, &acc);
+  if (dloss_dev != nullptr) check_dev_scalar(*dloss_dev, logits, "dloss_dev");
   auto dlogits = at::empty_like(logits);
   if (T == 0) return dlogits;
   acco_ce_bwd(logits.data_ptr(),
               reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
               lse.data_ptr<float>(), dlogits.data_ptr(),
-              acc.data_ptr<float>(), (float)dloss, nullptr, T, S, V,
-              (float)epsilon, cur_stream());
+              acc.data_ptr<float>(), (float)dloss,
+              dloss_dev != nullptr ? dloss_dev->data_ptr<float>() : nullptr,
+              T, S, V, (float)epsilon, cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return dlogits;
+}
+
+at::Tensor ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor lse,
+                  at::Tensor acc, double dloss, double epsilon) {
+  return ce_bwd_impl(logits, labels, lse, acc, dloss, nullptr, epsilon);
 }
 
 // dloss read from a 1-elem fp32 device tensor: no D2H sync in backward
 at::Tensor ce_bwd_dev(at::Tensor logits, at::Tensor labels, at::Tensor lse,
                       at::Tensor acc, at::Tensor dloss_dev, double epsilon) {
-  const auto [T, S, V] = check_ce_args(logits, labels, &lse, &acc);
-  TORCH_CHECK(dloss_dev.is_cuda() && dloss_dev.device() == logits.device() &&
-              dloss_dev.scalar_type() == at::kFloat && dloss_dev.numel() == 1,
-              "dloss_dev must be one fp32 on ", logits.device());
-  auto dlogits = at::empty_like(logits);
-  if (T == 0) return dlogits;
-  acco_ce_bwd(logits.data_ptr(),
-              reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
-              lse.data_ptr<float>(), dlogits.data_ptr(),
-              acc.data_ptr<float>(), 0.0f, dloss_dev.data_ptr<float>(), T, S,
-              V, (float)epsilon, cur_stream());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  return dlogits;
+  return ce_bwd_impl(logits, labels, lse, acc, 0.0, &dloss_dev, epsilon);
 }
 
-// ---- row-wise CE of the chunked lm_head + loss path
+// ---- the same kernels on rows (ce.hip): the chunked lm_head + loss path
 struct CeRowsShape { long long T; int V; };
 
 // The argument contract of the row-wise CE entry points: logits contiguous
@@ -538,22 +546,9 @@ static CeRowsShape check_ce_rows_args(const at::Tensor& logits,
               " = ", T, " elements on ", logits.device(), ", got ",
               targets.scalar_type(), " ", targets.sizes(), " on ",
               targets.device());
-  auto check_rowvec = [&](const at::Tensor& t, const char* name) {
-    TORCH_CHECK(t.is_cuda() && t.device() == logits.device() &&
-                t.scalar_type() == at::kFloat && t.is_contiguous() &&
-                t.numel() == T, name, " must be contiguous CUDA fp32 with T"
-                " = ", T, " elements on ", logits.device(), ", got ",
-                t.scalar_type(), " ", t.sizes(), " on ", t.device());
-  };
-  check_rowvec(lse, "lse");
-  if (tok_loss != nullptr) check_rowvec(*tok_loss, "tok_loss");
-  if (scale_dev != nullptr)
-    TORCH_CHECK(scale_dev->is_cuda() &&
-                scale_dev->device() == logits.device() &&
-                scale_dev->scalar_type() == at::kFloat &&
-                scale_dev->numel() == 1, "scale_dev must be one fp32 on ",
-                logits.device(), ", got ", scale_dev->scalar_type(), " ",
-                scale_dev->sizes(), " on ", scale_dev->device());
+  check_f32_vec(lse, T, logits, "lse");
+  if (tok_loss != nullptr) check_f32_vec(*tok_loss, T, logits, "tok_loss");
+  if (scale_dev != nullptr) check_dev_scalar(*scale_dev, logits, "scale_dev");
   return {(long long)T, (int)logits.size(1)};
 }
 

@@ -69,6 +69,14 @@ void acco_rope_qk_inplace(void* qkv, const float* cos_t, const float* sin_t,
                           hipStream_t stream);
 
 // ---- ce.hip
+// bf16 logits on a 16-byte aligned base (any V). A token is valid iff
+// 0 <= target < V; any other target (-100, >= V) is ignored: lse 0, no loss,
+// not counted in n_valid, zero dlogits row, never used as an index.
+//
+// Whole [B, S, V] logits, T = B·S: row t takes labels[t + 1], a sequence's
+// last position none. fwd stores lse[t] and atomicAdds {loss_sum, n_valid}
+// into the 128 zeroed shards of acc [128, 2]; bwd writes dlogits scaled by
+// (dloss_dev ? *dloss_dev : dloss) / max(acc[1], 1), acc the shards' sum.
 void acco_ce_fwd(const void* logits, const long long* labels, float* lse,
                  float* acc, long long T, int S, int V, float epsilon,
                  hipStream_t s);
@@ -76,12 +84,9 @@ void acco_ce_bwd(const void* logits, const long long* labels,
                  const float* lse, void* dlogits, const float* acc,
                  float dloss, const float* dloss_dev, long long T, int S,
                  int V, float epsilon, hipStream_t s);
-
-// ---- ce_rows.hip
-// bf16 rows [T, V] on a 16-byte aligned base (any V), targets[t] the label
-// of row t (valid iff 0 <= target < V); fwd stores lse[t] and tok_loss[t]
-// for every t (0 on ignored rows), bwd overwrites the rows with dlogits
-// scaled by the device scalar *scale_dev
+// Rows [T, V], targets[t] the label of row t: fwd stores lse[t] and
+// tok_loss[t] for every t (0 on ignored rows), bwd overwrites the rows with
+// dlogits scaled by the device scalar *scale_dev
 void acco_ce_rows_fwd(const void* logits, const long long* targets,
                       float* lse, float* tok_loss, long long T, int V,
                       float epsilon, hipStream_t s);

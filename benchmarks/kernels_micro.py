@@ -36,9 +36,50 @@ def report(name, sec, bytes_moved):
     print(f"{name:34s} {sec*1e6:9.1f} us   {bytes_moved/sec/1e12:6.2f} TB/s eff")
 
 
+def timeit_windows(fn, window=1.0, windows=3):
+    """Median seconds per call over `windows` timed windows of about
+    `window` seconds each (host clock around work that ends in a
+    synchronise; the iteration count comes from a short calibration)."""
+    iters = max(10, int(window / timeit(fn, iters=10, warmup=3)))
+    return sorted(timeit(fn, iters=iters, warmup=0)
+                  for _ in range(windows))[windows // 2]
+
+
+def bench_ce(ext):
+    """Fused causal-LM CE, both entry pairs, at T = 8 x 1024 rows: the
+    llama-1b head (V = 50304), the llama-3 vocabulary (128256) and GPT-Neo's
+    odd 50257, where all rows but every eighth start off a 16-byte boundary."""
+    B, S = 8, 1024
+    T = B * S
+    for V in (50304, 128256, 50257):
+        logits = torch.randn(B, S, V, device=DEV, dtype=torch.bfloat16)
+        labels = torch.randint(0, V, (B, S), device=DEV)
+        acc, lse = ext.ce_fwd(logits, labels)
+        report(f"ce_fwd (8x1024x{V})",
+               timeit_windows(lambda: ext.ce_fwd(logits, labels)), T * V * 2)
+        report(f"ce_bwd (8x1024x{V})",
+               timeit_windows(lambda: ext.ce_bwd(logits, labels, lse, acc,
+                                                 1.0)), T * V * 2 * 2)
+        rows = logits.view(T, V)
+        targets = labels.view(T)
+        tok = torch.empty(T, device=DEV)
+        scale = torch.ones(1, device=DEV)
+        report(f"ce_rows_fwd ({T}x{V})",
+               timeit_windows(lambda: ext.ce_rows_fwd(rows, targets, lse,
+                                                      tok)), T * V * 2)
+        # in place: from the second call on the rows hold dlogits of
+        # dlogits, which costs the same traffic and the same exps
+        report(f"ce_rows_bwd_ ({T}x{V})",
+               timeit_windows(lambda: ext.ce_rows_bwd_(rows, targets, lse,
+                                                       scale)), T * V * 2 * 2)
+        del logits, rows
+
+
 def main():
     torch.manual_seed(0)
     ext = ops.hip_ext()
+    if "--ce-only" in sys.argv[1:]:
+        return bench_ce(ext)
     B, S, D = 8, 1024, 2048          # llama-1b live shape
     R = B * S
 
@@ -119,16 +160,7 @@ def main():
     report("gelu_new bwd",
            timeit(lambda: ext.gelu_bwd(xg, xg)), xg.numel() * 2 * 3)
 
-    # ---- fused causal-LM CE (llama-1b head: vocab 50304)
-    V = 50304
-    logits = torch.randn(B, S, V, device=DEV, dtype=torch.bfloat16)
-    labels = torch.randint(0, V, (B, S), device=DEV)
-    acc, lse = ext.ce_fwd(logits, labels)
-    report("ce fwd (8x1024x50304)",
-           timeit(lambda: ext.ce_fwd(logits, labels)), B * S * V * 2)
-    report("ce bwd",
-           timeit(lambda: ext.ce_bwd(logits, labels, lse, acc, 1.0)),
-           B * S * V * 2 * 2)
+    bench_ce(ext)
 
     # ---- attention Delta
     o = torch.randn(B, S, H, Dh, device=DEV, dtype=torch.bfloat16)

@@ -1,8 +1,8 @@
-"""The row-wise CE kernels of the chunked lm_head + loss (ce_rows.hip:
-ce_rows_fwd, ce_rows_bwd_) against the fp64 references, tolerances and case
-list of streaming_ref.py: every case of ce_cases() (odd V with a different
-scalar head per row, more rows than the 8192-block grid, all rows ignored,
-large and -inf logits, label smoothing), V around the vector and block
+"""The row-wise CE kernels of the chunked lm_head + loss (ce.hip, Rows
+policy: ce_rows_fwd, ce_rows_bwd_) against the fp64 references, tolerances
+and case list of streaming_ref.py: every case of ce_cases() (odd V with a
+different scalar head per row, more rows than the 8192-block grid, all rows
+ignored, large and -inf logits, label smoothing), V around the vector and block
 strides with targets on every segment boundary of a misaligned row,
 out-of-range targets, bitwise reproducibility, the empty input and every
 argument check of both bindings.
@@ -108,14 +108,17 @@ def _peel(t, V):
     return min((-(t * V)) % 8, V)
 
 
-@pytest.mark.parametrize("eps", sr.CE_EPS)
-@pytest.mark.parametrize("V", [1, 7, 9, 2055, 2057])
-def test_ce_rows_alignment(V, eps):
-    """T = 5 rows of odd V: rows 1 to 4 start at four different offsets from
-    a 16-byte boundary. Targets on column 0, the last column of the scalar head, the
+ALIGN_V = [1, 7, 9, 2055, 2057]
+ALIGN_T = 5
+
+
+def alignment_inputs(V, eps):
+    """(logits [1, T + 1, V], labels [1, T + 1]) on the CPU, T = 5 rows of
+    odd V: rows 1 to 4 start at four different offsets from a 16-byte
+    boundary. Targets on column 0, the last column of the scalar head, the
     first vector column and V - 1, each in a misaligned row. A sixth, ignored
     row carries the shift of streaming_ref's labels and is not passed on."""
-    T = 5
+    T = ALIGN_T
     g = sr.case_generator("ce_rows_align_%d_%g" % (V, eps))
     logits = (torch.randn(1, T + 1, V, generator=g) * 2.0).bfloat16()
     assert len({(-(t * V)) % 8 for t in range(1, T)}) == 4
@@ -127,7 +130,14 @@ def test_ce_rows_alignment(V, eps):
     labels = torch.full((1, T + 1), -100)
     labels[0, 1:] = torch.tensor(targets)
     assert sr.ce_shift(labels).reshape(-1).tolist() == targets + [-100]
-    _check("align_V%d_eps%g" % (V, eps), logits, labels, eps, rows=T)
+    return logits, labels
+
+
+@pytest.mark.parametrize("eps", sr.CE_EPS)
+@pytest.mark.parametrize("V", ALIGN_V)
+def test_ce_rows_alignment(V, eps):
+    logits, labels = alignment_inputs(V, eps)
+    _check("align_V%d_eps%g" % (V, eps), logits, labels, eps, rows=ALIGN_T)
 
 
 # ------------------------------------------------------ out-of-range targets

@@ -1,4 +1,4 @@
-"""The chunked lm_head + loss (ops.linear_causal_lm_loss, ce_rows.hip) on the
+"""The chunked lm_head + loss (ops.linear_causal_lm_loss, ce.hip rows) on the
 GPU against fp64, next to the unfused path (F.linear + ops.causal_lm_loss /
 label_smoothed_causal_lm_loss) on the same inputs.
 

@@ -200,6 +200,56 @@ def test_ce(shape, eps, var):
     assert torch.equal(dlogits_host, dlogits)
 
 
+@pytest.mark.parametrize("V", [72, 2057])
+def test_ce_out_of_range_label_is_ignored(V):
+    """A label outside [0, V) is an ignored token, as -100 is: lse 0, a zero
+    dlogits row, not counted, and never used as an index."""
+    eps = 0.1
+    g = sr.case_generator("ce_bad_label_%d" % V)
+    logits = (torch.randn(1, 5, V, generator=g) * 2.0).bfloat16().cuda()
+    valid = int(torch.randint(0, V, (1,), generator=g))
+    bad = torch.tensor([[0, V, 2 ** 40, -(2 ** 40), valid]]).cuda()
+    ignored = torch.tensor([[0, -100, -100, -100, valid]]).cuda()
+    ext = _ext()
+    dloss_dev = torch.tensor([sr.CE_DLOSS], device="cuda")
+
+    def run(labels):
+        acc, lse = ext.ce_fwd(logits, labels, eps)
+        return lse, acc[1], ext.ce_bwd_dev(logits, labels, lse, acc,
+                                           dloss_dev, eps)
+
+    lse, n_valid, dlogits = run(bad)
+    for got, want in zip((lse, n_valid, dlogits), run(ignored)):
+        assert torch.equal(got, want)
+    assert float(n_valid) == 1.0
+    assert not lse[:3].any() and not dlogits[0, :3].any()
+    assert float(lse[3]) != 0.0 and dlogits[0, 3].any()
+
+
+def test_causal_lm_loss_takes_logits_off_16_bytes():
+    """ops.causal_lm_loss on a contiguous view that starts one bf16 element
+    into its buffer (the bindings reject it, the autograd function copies
+    it): the gradient of its aligned clone bit for bit; the loss, summed
+    with atomics, within tol_loss of the clone's."""
+    from acco_amd import ops
+    B, S_, V = 2, 5, 72
+    logits, labels = sr.ce_inputs((B, S_, V), 0.0, "n2")
+    tol = sr.ce_tolerances(logits, labels, 0.0)["tol_loss"]
+    buf = torch.zeros(B * S_ * V + 1, device="cuda", dtype=torch.bfloat16)
+    buf[1:] = logits.flatten().cuda()
+    off = buf[1:].view(B, S_, V).requires_grad_(True)
+    aligned = off.detach().clone().requires_grad_(True)
+    assert off.is_contiguous() and off.data_ptr() % 16 == 2
+    assert aligned.data_ptr() % 16 == 0
+    lb = labels.cuda()
+    loss_off = ops.causal_lm_loss(off, lb)
+    loss_off.backward()
+    loss = ops.causal_lm_loss(aligned, lb)
+    loss.backward()
+    assert off.grad.any() and torch.equal(off.grad, aligned.grad)
+    assert abs(float(loss_off.detach()) - float(loss.detach())) <= tol
+
+
 # ---------------------------------------------------------------- AdamW
 _ADAMW_CASES = sr.adamw_cases()
 _DT = {"bf16": torch.bfloat16, "fp32": torch.float32}
@@ -398,6 +448,8 @@ def _rope_packed(dst=(1, 8, 64), off=16, Hsec=2, D=16, cos=(8, 16),
 
 _labels32 = lambda: torch.zeros(2, 4, device="cuda", dtype=torch.int32)
 _labels = lambda *shape: torch.zeros(*shape, device="cuda", dtype=torch.long)
+# contiguous [2, 4, 16] starting one bf16 element into its buffer
+_logits_off_one = lambda: _bf16(2 * 4 * 16 + 1)[1:].view(2, 4, 16)
 
 REJECTED = {
     "adamw_m_fp64": _adamw(m=lambda: _f32(8).double()),
@@ -464,6 +516,10 @@ REJECTED = {
     "ce_fwd_labels_transposed":
         _ce_call("ce_fwd", labels=lambda: _labels(4, 2).t()),
     "ce_fwd_V_0": _ce_call("ce_fwd", V=0),
+    "ce_fwd_logits_off_16_bytes": _ce_call("ce_fwd", logits=_logits_off_one),
+    "ce_bwd_logits_off_16_bytes": _ce_call("ce_bwd", logits=_logits_off_one),
+    "ce_bwd_dev_logits_off_16_bytes":
+        _ce_call("ce_bwd_dev", logits=_logits_off_one),
     "ce_bwd_labels_other_S": _ce_call("ce_bwd", labels=lambda: _labels(2, 3)),
     "ce_bwd_labels_int32": _ce_call("ce_bwd", labels=_labels32),
     "ce_bwd_lse_short": _ce_call("ce_bwd", lse=lambda: _f32(7)),
