@@ -22,6 +22,7 @@ import torch.nn as nn
 from acco_amd import ops
 from acco_amd.models.fuse import arena_linear, arena_lm_loss
 from acco_amd.models.config import GPTNeoConfig
+from acco_amd.models.kv_cache import prefill
 
 
 class GPTNeoSelfAttention(nn.Module):
@@ -38,7 +39,11 @@ class GPTNeoSelfAttention(nn.Module):
 
     def forward(self, x: torch.Tensor,
                 doc_start: Optional[torch.Tensor] = None,
-                doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
+                doc_end: Optional[torch.Tensor] = None,
+                kv=None) -> torch.Tensor:
+        """`kv` = (k_cache, v_cache, cache_len), prefill only: K and V of
+        every position are also appended to the cache; None (the training
+        forward) launches nothing for it."""
         B, S, d = x.shape
         H, hd = self.cfg.num_heads, self.cfg.head_dim
         if self._fused_kvq is not None:
@@ -56,6 +61,11 @@ class GPTNeoSelfAttention(nn.Module):
                 doc = () if doc_start is None else (doc_start, doc_end)
                 o = AttnQKVPackedFn.apply(kvq, None, None, H, H, hd, 1.0,
                                           window, offs, *doc)
+                if kv is not None:
+                    _ops.kv_append(
+                        kv[0], kv[1], kv[2],
+                        kvq[..., :d].unflatten(-1, (H, hd)),
+                        kvq[..., d:2 * d].unflatten(-1, (H, hd)))
                 return arena_linear(self.out_proj, o)
             k, v, q = torch.split(kvq, splits, dim=-1)
             q = q.contiguous().view(B, S, H, hd)
@@ -66,12 +76,33 @@ class GPTNeoSelfAttention(nn.Module):
             k = self.k_proj(x).view(B, S, H, hd)
             v = self.v_proj(x).view(B, S, H, hd)
         window = self.cfg.window_size if self.attention_type == "local" else None
+        if kv is not None:
+            ops.kv_append(kv[0], kv[1], kv[2], k, v)
         if doc_start is None:
             o = ops.causal_attention(q, k, v, scale=1.0, window=window)
         else:
             o = ops.causal_attention(q, k, v, scale=1.0, window=window,
                                      doc_start=doc_start, doc_end=doc_end)
         return arena_linear(self.out_proj, o.reshape(B, S, d))
+
+    def decode(self, x: torch.Tensor, cache, layer: int,
+               lens1: torch.Tensor) -> torch.Tensor:
+        """One token per sequence, x [B, 1, hidden]: project, append K and V
+        to layer `layer` of the cache at cache.lens[b], attend the lens1 =
+        lens + 1 cached tokens (the last window_size of them in a local
+        layer). Uses the per-projection weights, which alias the arena when
+        one is installed."""
+        B = x.shape[0]
+        H, hd = self.cfg.num_heads, self.cfg.head_dim
+        q = self.q_proj(x).view(B, H, hd)
+        k = self.k_proj(x).view(B, 1, H, hd)
+        v = self.v_proj(x).view(B, 1, H, hd)
+        kc, vc = cache.k[layer], cache.v[layer]
+        ops.kv_append(kc, vc, cache.lens, k, v)
+        window = (self.cfg.window_size
+                  if self.attention_type == "local" else None)
+        o = ops.decode_attention(q, kc, vc, lens1, scale=1.0, window=window)
+        return arena_linear(self.out_proj, o.reshape(B, 1, -1))
 
 
 class GPTNeoAttention(nn.Module):
@@ -81,7 +112,9 @@ class GPTNeoAttention(nn.Module):
         super().__init__()
         self.attention = GPTNeoSelfAttention(cfg, cfg.layer_attention_type(layer_id))
 
-    def forward(self, x, doc_start=None, doc_end=None):
+    def forward(self, x, doc_start=None, doc_end=None, kv=None):
+        if kv is not None:
+            return self.attention(x, doc_start, doc_end, kv)
         return self.attention(x, doc_start, doc_end)
 
 
@@ -103,13 +136,22 @@ class GPTNeoBlock(nn.Module):
         self.ln_2 = nn.LayerNorm(cfg.hidden_size, eps=cfg.layer_norm_epsilon)
         self.mlp = GPTNeoMLP(cfg)
 
-    def forward(self, pending, residual, doc_start=None, doc_end=None):
+    def forward(self, pending, residual, doc_start=None, doc_end=None,
+                kv=None, decode=None):
         """(pending, residual) form — every residual add fused into the
         following LayerNorm kernel (see LlamaDecoderLayer); returns the
-        un-added MLP output + running residual, ln_f completes the last add."""
+        un-added MLP output + running residual, ln_f completes the last add.
+        `kv` (prefill) is handed to the attention; `decode` = (cache, layer
+        index, lens + 1) makes this a single-token step on the cache. Both
+        None: the training forward."""
         h1, residual = ops.add_layer_norm(pending, residual, self.ln_1.weight,
                                           self.ln_1.bias, self.ln_1.eps)
-        a = self.attn(h1, doc_start, doc_end)
+        if decode is not None:
+            a = self.attn.attention.decode(h1, *decode)
+        elif kv is not None:
+            a = self.attn(h1, doc_start, doc_end, kv)
+        else:
+            a = self.attn(h1, doc_start, doc_end)
         h2, residual = ops.add_layer_norm(a, residual, self.ln_2.weight,
                                           self.ln_2.bias, self.ln_2.eps)
         return self.mlp(h2), residual
@@ -127,9 +169,22 @@ class GPTNeoModel(nn.Module):
         self.gradient_checkpointing = False
 
     def forward(self, input_ids: torch.Tensor,
-                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+                doc_start: Optional[torch.Tensor] = None,
+                cache=None) -> torch.Tensor:
+        """`cache` (a KVCache, prefill only): every layer appends its K / V
+        to it at cache.lens. None: the training forward, unchanged."""
         S = input_ids.shape[1]
         pos = torch.arange(S, device=input_ids.device)
+        if cache is not None:
+            pending = self.wte(input_ids) + self.wpe(pos)[None]
+            residual = None
+            for i, block in enumerate(self.h):
+                pending, residual = block(
+                    pending, residual,
+                    kv=(cache.k[i], cache.v[i], cache.lens))
+            y, _ = ops.add_layer_norm(pending, residual, self.ln_f.weight,
+                                      self.ln_f.bias, self.ln_f.eps)
+            return y
         doc = ()
         if doc_start is None:
             pending = self.wte(input_ids) + self.wpe(pos)[None]
@@ -155,6 +210,23 @@ class GPTNeoModel(nn.Module):
         y, _ = ops.add_layer_norm(pending, residual, self.ln_f.weight,
                                   self.ln_f.bias, self.ln_f.eps)
         return y
+
+    def decode_step(self, tokens: torch.Tensor, cache) -> torch.Tensor:
+        """Hidden state [B, hidden] of one new token per sequence at position
+        cache.lens[b] (wpe is read there; the host-side step count keeps it
+        below max_len); appends to every layer of the cache and advances
+        cache.lens once, after the last layer."""
+        pos = cache.lens.long().clamp(0, self.wpe.num_embeddings - 1)
+        pending = (self.wte(tokens) + self.wpe(pos))[:, None]
+        residual = None
+        lens1 = cache.lens + 1
+        for i, block in enumerate(self.h):
+            pending, residual = block(pending, residual,
+                                      decode=(cache, i, lens1))
+        y, _ = ops.add_layer_norm(pending, residual, self.ln_f.weight,
+                                  self.ln_f.bias, self.ln_f.eps)
+        cache.lens = lens1
+        return y[:, 0]
 
 
 class GPTNeoForCausalLM(nn.Module):
@@ -208,3 +280,21 @@ class GPTNeoForCausalLM(nn.Module):
         loss = ops.label_smoothed_causal_lm_loss(logits, labels,
                                                  label_smoothing)
         return (loss, logits)
+
+    @torch.no_grad()
+    def prefill(self, input_ids: torch.Tensor, lens: Optional[torch.Tensor],
+                cache) -> torch.Tensor:
+        """Run the prompt [B, S] (sequence b holds lens[b] <= S tokens, the
+        rest is right-padding; None = all S) through the blocks, fill `cache`
+        and return the logits [B, V] of each sequence's last prompt token."""
+        return prefill(self, self.transformer, input_ids, lens, cache)
+
+    @torch.no_grad()
+    def decode_step(self, tokens: torch.Tensor, cache) -> torch.Tensor:
+        """Logits [B, V] after one more token per sequence, tokens [B], given
+        everything already in `cache`; raises ValueError once the cache is
+        full (a host-side count, no device read)."""
+        cache.room_for(1)
+        hidden = self.transformer.decode_step(tokens, cache)
+        cache.steps += 1
+        return arena_linear(self.lm_head, hidden)

@@ -21,6 +21,7 @@ import torch.nn as nn
 from acco_amd import ops
 from acco_amd.models.config import LlamaConfig
 from acco_amd.models.fuse import arena_linear, arena_lm_loss
+from acco_amd.models.kv_cache import prefill
 
 
 class LlamaRMSNorm(nn.Module):
@@ -46,7 +47,11 @@ class LlamaAttention(nn.Module):
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                 doc_start: Optional[torch.Tensor] = None,
-                doc_end: Optional[torch.Tensor] = None) -> torch.Tensor:
+                doc_end: Optional[torch.Tensor] = None,
+                kv=None) -> torch.Tensor:
+        """`kv` = (k_cache, v_cache, cache_len), prefill only: the post-RoPE
+        K and V of every position are also appended to the cache; None (the
+        training forward) launches nothing for it."""
         B, S, _ = x.shape
         cfg = self.cfg
         # keep everything in the projections' natural [B, S, H, D] layout:
@@ -65,9 +70,15 @@ class LlamaAttention(nn.Module):
                         (cfg.num_heads + cfg.num_kv_heads) * hd)
                 # rotates qkv's q|k sections in place; returns (o, qkv)
                 doc = () if doc_start is None else (doc_start, doc_end)
-                o, _ = AttnQKVPackedFn.apply(qkv, cos, sin, cfg.num_heads,
-                                             cfg.num_kv_heads, hd,
-                                             hd ** -0.5, 0, offs, *doc)
+                o, roped = AttnQKVPackedFn.apply(qkv, cos, sin, cfg.num_heads,
+                                                 cfg.num_kv_heads, hd,
+                                                 hd ** -0.5, 0, offs, *doc)
+                if kv is not None:
+                    kw = cfg.num_kv_heads * hd
+                    ops.kv_append(
+                        kv[0], kv[1], kv[2],
+                        roped[..., offs[1]:offs[1] + kw].unflatten(-1, (-1, hd)),
+                        roped[..., offs[2]:offs[2] + kw].unflatten(-1, (-1, hd)))
                 return arena_linear(self.o_proj, o)
             q, k, v = torch.split(qkv, splits, dim=-1)
             q = q.contiguous().view(B, S, cfg.num_heads, cfg.head_dim)
@@ -78,12 +89,31 @@ class LlamaAttention(nn.Module):
             k = self.k_proj(x).view(B, S, cfg.num_kv_heads, cfg.head_dim)
             v = self.v_proj(x).view(B, S, cfg.num_kv_heads, cfg.head_dim)
         q, k = ops.rope_apply(q, k, cos, sin)
+        if kv is not None:
+            ops.kv_append(kv[0], kv[1], kv[2], k, v)
         if doc_start is None:
             o = ops.causal_attention(q, k, v)      # [B, S, H, D]
         else:
             o = ops.causal_attention(q, k, v, doc_start=doc_start,
                                      doc_end=doc_end)
         return arena_linear(self.o_proj, o.reshape(B, S, -1))
+
+    def decode(self, x: torch.Tensor, cache, layer: int,
+               lens1: torch.Tensor) -> torch.Tensor:
+        """One token per sequence, x [B, 1, hidden]: project, append K (RoPE
+        at position cache.lens[b]) and V to layer `layer` of the cache,
+        attend the lens1 = lens + 1 cached tokens. Uses the per-projection
+        weights, which alias the arena when one is installed."""
+        B = x.shape[0]
+        cfg, hd = self.cfg, self.cfg.head_dim
+        q = self.q_proj(x).view(B, 1, cfg.num_heads, hd)
+        k = self.k_proj(x).view(B, 1, cfg.num_kv_heads, hd)
+        v = self.v_proj(x).view(B, 1, cfg.num_kv_heads, hd)
+        cos, sin = cache.rope
+        kc, vc = cache.k[layer], cache.v[layer]
+        q = ops.kv_append(kc, vc, cache.lens, k, v, q, cos, sin)
+        o = ops.decode_attention(q[:, 0], kc, vc, lens1)
+        return arena_linear(self.o_proj, o.reshape(B, 1, -1))
 
 
 class LlamaMLP(nn.Module):
@@ -125,11 +155,19 @@ class LlamaDecoderLayer(nn.Module):
         self.post_attention_layernorm = LlamaRMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
     def forward(self, pending, residual, cos, sin, doc_start=None,
-                doc_end=None):
+                doc_end=None, kv=None, decode=None):
+        """`kv` (prefill) is handed to the attention; `decode` = (cache,
+        layer index, lens + 1) makes this a single-token step on the cache.
+        Both None: the training forward."""
         n1 = self.input_layernorm
         h1, residual = ops.add_rms_norm(pending, residual, n1.weight,
                                         n1.variance_epsilon)
-        a = self.self_attn(h1, cos, sin, doc_start, doc_end)
+        if decode is not None:
+            a = self.self_attn.decode(h1, *decode)
+        elif kv is not None:
+            a = self.self_attn(h1, cos, sin, doc_start, doc_end, kv)
+        else:
+            a = self.self_attn(h1, cos, sin, doc_start, doc_end)
         n2 = self.post_attention_layernorm
         h2, residual = ops.add_rms_norm(a, residual, n2.weight,
                                         n2.variance_epsilon)
@@ -162,10 +200,21 @@ class LlamaModel(nn.Module):
         return hit
 
     def forward(self, input_ids: torch.Tensor,
-                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+                doc_start: Optional[torch.Tensor] = None,
+                cache=None) -> torch.Tensor:
+        """`cache` (a KVCache, prefill only): every layer appends its K / V
+        to it at cache.lens. None: the training forward, unchanged."""
         pending = self.embed_tokens(input_ids)
         residual = None
         cos, sin = self._cos_sin(input_ids.shape[1], pending.device)
+        if cache is not None:
+            for i, layer in enumerate(self.layers):
+                pending, residual = layer(
+                    pending, residual, cos, sin,
+                    kv=(cache.k[i], cache.v[i], cache.lens))
+            y, _ = ops.add_rms_norm(pending, residual, self.norm.weight,
+                                    self.norm.variance_epsilon)
+            return y
         # Document masking of packed rows: RoPE positions stay ABSOLUTE.
         # A rotated q·k depends only on the distance between the two
         # positions, and attention never leaves a document, so every score is
@@ -191,6 +240,21 @@ class LlamaModel(nn.Module):
         y, _ = ops.add_rms_norm(pending, residual, self.norm.weight,
                                 self.norm.variance_epsilon)
         return y
+
+    def decode_step(self, tokens: torch.Tensor, cache) -> torch.Tensor:
+        """Hidden state [B, hidden] of one new token per sequence at position
+        cache.lens[b]; appends to every layer of the cache and advances
+        cache.lens once, after the last layer."""
+        pending = self.embed_tokens(tokens)[:, None]
+        residual = None
+        lens1 = cache.lens + 1
+        for i, layer in enumerate(self.layers):
+            pending, residual = layer(pending, residual, None, None,
+                                      decode=(cache, i, lens1))
+        y, _ = ops.add_rms_norm(pending, residual, self.norm.weight,
+                                self.norm.variance_epsilon)
+        cache.lens = lens1
+        return y[:, 0]
 
 
 class LlamaForCausalLM(nn.Module):
@@ -245,3 +309,21 @@ class LlamaForCausalLM(nn.Module):
         loss = ops.label_smoothed_causal_lm_loss(logits, labels,
                                                  label_smoothing)
         return (loss, logits)
+
+    @torch.no_grad()
+    def prefill(self, input_ids: torch.Tensor, lens: Optional[torch.Tensor],
+                cache) -> torch.Tensor:
+        """Run the prompt [B, S] (sequence b holds lens[b] <= S tokens, the
+        rest is right-padding; None = all S) through the layers, fill `cache`
+        and return the logits [B, V] of each sequence's last prompt token."""
+        return prefill(self, self.model, input_ids, lens, cache)
+
+    @torch.no_grad()
+    def decode_step(self, tokens: torch.Tensor, cache) -> torch.Tensor:
+        """Logits [B, V] after one more token per sequence, tokens [B], given
+        everything already in `cache`; raises ValueError once the cache is
+        full (a host-side count, no device read)."""
+        cache.room_for(1)
+        hidden = self.model.decode_step(tokens, cache)
+        cache.steps += 1
+        return arena_linear(self.lm_head, hidden)

@@ -214,6 +214,67 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                              doc_end.to(torch.int32).contiguous())
 
 
+# ------------------------------------------------ KV cache (generation)
+
+def _decode_contract(q_heads: int, k_cache: torch.Tensor) -> bool:
+    """What the cache kernels take: bf16, D in {64, 128}, 1 <= H/Hkv <= 8."""
+    Hkv, D = k_cache.shape[1], k_cache.shape[3]
+    return (k_cache.dtype == torch.bfloat16 and D in (64, 128)
+            and q_heads % Hkv == 0 and 1 <= q_heads // Hkv <= 8)
+
+
+def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
+              cache_len: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+              q: Optional[torch.Tensor] = None,
+              cos: Optional[torch.Tensor] = None,
+              sin: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Append k, v [B, T, Hkv, D] to the caches [B, Hkv, Smax, D] at row
+    cache_len[b] + t, in place; rows at or beyond Smax are dropped and
+    `cache_len` (int32 [B], on the device) is left alone (torch_ref.kv_append
+    has the semantics). With cos / sin ([>= Smax, D] fp32) K is rotated by its
+    absolute position and the rotated `q` [B, T, H, D] is returned.
+
+    k, v and q may be views of the packed projection output (a column
+    section `[..., off:off + h*D]` viewed as [B, T, h, D]): the HIP kernel
+    reads them through their row stride, no copies. One launch, no host
+    sync."""
+    heads = q.shape[2] if q is not None else k_cache.shape[1]
+    if (_use_ref(k_cache, "kv_append") or k.dtype != torch.bfloat16
+            or not _decode_contract(heads, k_cache)):
+        return torch_ref.kv_append(k_cache, v_cache, cache_len, k, v, q,
+                                   cos, sin)
+    return hip_ext().kv_append(q if cos is not None else None, k, v, cos,
+                               sin, k_cache, v_cache, cache_len)
+
+
+def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, cache_len: torch.Tensor,
+                     scale: Optional[float] = None,
+                     window: Optional[int] = None) -> torch.Tensor:
+    """o [B, H, D] of one query token per sequence, q [B, H, D], against the
+    caches [B, Hkv, Smax, D]: the query is the last of cache_len[b] cached
+    tokens and attends keys [max(0, L - window), L), L = clamp(cache_len[b],
+    0, Smax) (torch_ref.decode_attention has the semantics). HIP
+    flash-decoding kernel for bf16, D in {64, 128}, 1 <= H/Hkv <= 8; the
+    torch reference outside that contract. No host sync."""
+    if (_use_ref(q, "attn_decode") or q.dtype != torch.bfloat16
+            or not _decode_contract(q.shape[1], k_cache)):
+        return torch_ref.decode_attention(q, k_cache, v_cache, cache_len,
+                                          scale=scale, window=window)
+    if scale is None:
+        scale = q.shape[2] ** -0.5
+    return hip_ext().attn_decode(q, k_cache, v_cache, cache_len,
+                                 float(scale), int(window or 0))
+
+
+def decode_attention_splits(bhkv: int, smax: int) -> Tuple[int, int]:
+    """(n_split, chunk) of the HIP decode attention for B·Hkv (sequence, kv
+    head) pairs and a cache of Smax rows: workgroup i of a pair owns keys
+    [i·chunk, (i+1)·chunk). A host function of its two arguments only."""
+    n_split, chunk = hip_ext().attn_decode_grid(int(bhkv), int(smax))
+    return int(n_split), int(chunk)
+
+
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     if _use_ref(logits, "ce_fwd"):
         return torch_ref.causal_lm_loss(logits, labels)

@@ -1004,9 +1004,162 @@ std::vector<at::Tensor> attn_bwd_packed(at::Tensor qkv, at::Tensor dO,
   return {dkq, dvq};
 }
 
+// ---- KV cache: append and single-token attention
+struct CacheShape { int B, Hkv, Smax, D; };
+
+// The argument contract of both cache entry points: k_cache and v_cache
+// contiguous CUDA bf16 [B, Hkv, Smax, D] on one device, 16-byte aligned,
+// D in {64, 128}; cache_len contiguous int32 [B] on that device (data: the
+// kernels clamp it into [0, Smax]).
+static CacheShape check_cache_args(const at::Tensor& k_cache,
+                                   const at::Tensor& v_cache,
+                                   const at::Tensor& cache_len) {
+  CHECK_BF16_CONTIG(k_cache); CHECK_BF16_CONTIG(v_cache);
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+              v_cache.device() == k_cache.device(),
+              "k_cache and v_cache must be [B, Hkv, Smax, D] of one shape on "
+              "one device, got ", k_cache.sizes(), " on ", k_cache.device(),
+              " and ", v_cache.sizes(), " on ", v_cache.device());
+  const int64_t B = k_cache.size(0), Hkv = k_cache.size(1);
+  const int64_t Smax = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK((D == 64 || D == 128) && D % 16 == 0,
+              "k_cache: need D in {64, 128}, got D=", D);
+  TORCH_CHECK(B > 0 && Hkv > 0 && Smax > 0 && Smax < (1LL << 30) &&
+              B * Hkv <= 65535, "k_cache: need 1 <= B*Hkv <= 65535 and "
+              "1 <= Smax < 2^30, got ", k_cache.sizes());
+  TORCH_CHECK(aligned_to(k_cache, 16) && aligned_to(v_cache, 16),
+              "k_cache and v_cache must be 16-byte aligned");
+  TORCH_CHECK(cache_len.is_cuda() && cache_len.device() == k_cache.device() &&
+              cache_len.scalar_type() == at::kInt &&
+              cache_len.is_contiguous() && cache_len.dim() == 1 &&
+              cache_len.size(0) == B, "cache_len must be contiguous int32 [B]"
+              " = [", B, "] on ", k_cache.device(), ", got ",
+              cache_len.scalar_type(), " ", cache_len.sizes(), " on ",
+              cache_len.device());
+  return {(int)B, (int)Hkv, (int)Smax, (int)D};
+}
+
+// t [B, T, heads, D] bf16 on ref's device whose heads are contiguous inside a
+// token row and whose rows lie one row stride apart (a section of the packed
+// projection output, or a contiguous tensor); returns the row stride
+static long long check_token_rows(const at::Tensor& t, const at::Tensor& ref,
+                                  int64_t B, int64_t T, int64_t heads,
+                                  int64_t D, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device() &&
+              t.scalar_type() == at::kBFloat16, name, " must be CUDA bf16 on ",
+              ref.device(), ", got ", t.scalar_type(), " on ", t.device());
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == T &&
+              t.size(2) == heads && t.size(3) == D, name, " must be [", B,
+              ", ", T, ", ", heads, ", ", D, "], got ", t.sizes());
+  const int64_t rs = T > 1 ? t.stride(1) : (B > 1 ? t.stride(0) : heads * D);
+  TORCH_CHECK(t.stride(3) == 1 && t.stride(2) == D && rs >= heads * D &&
+              rs % 8 == 0 && (B == 1 || t.stride(0) == T * rs) &&
+              (T == 1 || t.stride(1) == rs), name, " must have contiguous "
+              "heads and evenly strided token rows (row stride a multiple of "
+              "8), got strides ", t.strides());
+  TORCH_CHECK(aligned_to(t, 16), name, " must be 16-byte aligned");
+  return rs;
+}
+
+// Writes k / v of T new tokens per sequence into the caches at row
+// cache_len[b] + t (rows >= Smax dropped); with cos / sin, K is rotated by
+// its absolute position and the rotated q [B, T, H, D] is returned.
+c10::optional<at::Tensor> kv_append(c10::optional<at::Tensor> q, at::Tensor k,
+                                    at::Tensor v,
+                                    c10::optional<at::Tensor> cos_t,
+                                    c10::optional<at::Tensor> sin_t,
+                                    at::Tensor k_cache, at::Tensor v_cache,
+                                    at::Tensor cache_len) {
+  const auto [B, Hkv, Smax, D] = check_cache_args(k_cache, v_cache, cache_len);
+  TORCH_CHECK(k.dim() == 4, "k must be [B, T, Hkv, D], got ", k.sizes());
+  const int64_t T = k.size(1);
+  TORCH_CHECK(T >= 0 && T < (1LL << 30), "k: T out of range: ", T);
+  const long long k_rs = check_token_rows(k, k_cache, B, T, Hkv, D, "k");
+  const long long v_rs = check_token_rows(v, k_cache, B, T, Hkv, D, "v");
+  TORCH_CHECK(cos_t.has_value() == sin_t.has_value(),
+              "cos and sin must both be given or both be None");
+  TORCH_CHECK(cos_t.has_value() == q.has_value(),
+              "q is rotated with the tables: give q, cos and sin, or none");
+  if (!cos_t.has_value()) {
+    TORCH_CHECK((long long)B * T * 2 * Hkv * (D / 16) < (1LL << 31),
+                "k: too many elements for one launch");
+    if (T == 0) return c10::nullopt;
+    acco_kv_append(nullptr, k.data_ptr(), v.data_ptr(), nullptr,
+                   k_cache.data_ptr(), v_cache.data_ptr(),
+                   cache_len.data_ptr<int>(), nullptr, nullptr, B, (int)T, 0,
+                   Hkv, D, Smax, 0, 0, k_rs, v_rs, cur_stream());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    return c10::nullopt;
+  }
+  TORCH_CHECK(q->dim() == 4 && q->size(2) > 0 && q->size(2) % Hkv == 0,
+              "q must be [B, T, H, D] with H % Hkv == 0, got ", q->sizes());
+  const int64_t H = q->size(2);
+  const long long q_rs = check_token_rows(*q, k_cache, B, T, H, D, "q");
+  check_rope_table(*cos_t, *sin_t, Smax, D, k_cache);
+  TORCH_CHECK(cos_t->size(0) < (1LL << 31), "cos: too many rows");
+  TORCH_CHECK((long long)B * T * (H + 2 * Hkv) * (D / 16) < (1LL << 31),
+              "q: too many elements for one launch");
+  auto q_out = at::empty({B, T, H, D}, k_cache.options());
+  if (T == 0) return q_out;
+  acco_kv_append(q->data_ptr(), k.data_ptr(), v.data_ptr(), q_out.data_ptr(),
+                 k_cache.data_ptr(), v_cache.data_ptr(),
+                 cache_len.data_ptr<int>(), cos_t->data_ptr<float>(),
+                 sin_t->data_ptr<float>(), B, (int)T, (int)H, Hkv, D, Smax,
+                 (int)cos_t->size(0), q_rs, k_rs, v_rs, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return q_out;
+}
+
+// (n_split, chunk) of attn_decode for B*Hkv (sequence, kv head) pairs and a
+// cache of Smax rows: split i owns keys [i*chunk, (i+1)*chunk)
+std::vector<int64_t> attn_decode_grid(int64_t BHkv, int64_t Smax) {
+  TORCH_CHECK(BHkv > 0 && Smax > 0 && Smax < (1LL << 30),
+              "need BHkv > 0 and 0 < Smax < 2^30, got BHkv=", BHkv, " Smax=",
+              Smax);
+  int n_split, chunk;
+  acco_attn_decode_grid((long long)BHkv, (int)Smax, &n_split, &chunk);
+  return {n_split, chunk};
+}
+
+// o [B, H, D] of one query token per sequence: q [B, H, D] bf16 whose rows
+// may be strided (a section of the packed projection output). A window at or
+// beyond Smax bounds nothing and reaches the kernel as 0 (none).
+at::Tensor attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
+                       at::Tensor cache_len, double scale, int64_t window) {
+  const auto [B, Hkv, Smax, D] = check_cache_args(k_cache, v_cache, cache_len);
+  TORCH_CHECK(q.dim() == 3, "q must be [B, H, D], got ", q.sizes());
+  const int64_t H = q.size(1);
+  TORCH_CHECK(H > 0 && H % Hkv == 0 && H / Hkv <= 8,
+              "q: need H % Hkv == 0 and 1 <= H/Hkv <= 8, got H=", H, " Hkv=",
+              Hkv);
+  const long long q_rs =
+      check_token_rows(q.unsqueeze(1), k_cache, B, 1, H, D, "q");
+  TORCH_CHECK(window >= 0, "window must be >= 0, got ", window);
+  const int win = window >= Smax ? 0 : (int)window;
+  int n_split, chunk;
+  acco_attn_decode_grid((long long)B * Hkv, Smax, &n_split, &chunk);
+  auto o = at::empty({B, H, D}, k_cache.options());
+  auto ws = at::empty({(int64_t)B * H * n_split * (2 + D)},
+                      k_cache.options().dtype(at::kFloat));
+  acco_attn_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                   cache_len.data_ptr<int>(), o.data_ptr(),
+                   ws.data_ptr<float>(), B, (int)H, Hkv, D, Smax,
+                   (float)scale, win, q_rs, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return o;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("kv_append", &kv_append, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("cos"), py::arg("sin"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("cache_len"));
+  m.def("attn_decode_grid", &attn_decode_grid, py::arg("BHkv"),
+        py::arg("Smax"));
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("cache_len"), py::arg("scale"),
+        py::arg("window"));
   m.def("fused_adamw", &fused_adamw,
         "Fused sharded AdamW (gfx950): cast+scale+AdamW+bf16 writeout; "
         "commit=false = ACCO tentative step");

@@ -68,6 +68,33 @@ void acco_rope_qk_inplace(void* qkv, const float* cos_t, const float* sin_t,
                           long long W, long long q_off, long long k_off,
                           hipStream_t stream);
 
+// KV-cache append of T tokens per sequence: k / v (row strides k_rs / v_rs,
+// heads contiguous inside a row) into caches [B, Hkv, Smax, D] at row
+// clamp(cache_len[b], 0, Smax) + t, rows >= Smax dropped. cos_t / sin_t
+// (fp32 [table_rows >= Smax, D]) non-null: K rotated by its absolute
+// position, rotated q (row stride q_rs) stored to q_out [B, T, H, D]; null:
+// K copied, q and q_out unused. cache_len (int32 [B], device) is not modified.
+void acco_kv_append(const void* q, const void* k, const void* v, void* q_out,
+                    void* k_cache, void* v_cache, const int* cache_len,
+                    const float* cos_t, const float* sin_t, int B, int T,
+                    int H, int Hkv, int D, int Smax, int table_rows,
+                    long long q_rs, long long k_rs, long long v_rs,
+                    hipStream_t stream);
+
+// ---- attention_decode.hip
+// One query token per sequence against the cache: q [B, H, D] (row stride
+// q_rs), caches [B, Hkv, Smax, D], keys [max(0, L - window), L) with
+// L = clamp(cache_len[b], 0, Smax), window 0 = none; D in {64, 128},
+// 1 <= H / Hkv <= 8. The key range is split over n_split workgroups of
+// `chunk` keys each (host only, a function of B * Hkv and Smax); workspace:
+// B * H * n_split * (2 + D) fp32, written before it is read.
+void acco_attn_decode_grid(long long BHkv, int Smax, int* n_split,
+                           int* chunk);
+void acco_attn_decode(const void* q, const void* k_cache, const void* v_cache,
+                      const int* cache_len, void* o, float* workspace, int B,
+                      int H, int Hkv, int D, int Smax, float scale,
+                      int window, long long q_rs, hipStream_t stream);
+
 // ---- ce.hip
 // bf16 logits on a 16-byte aligned base (any V). A token is valid iff
 // 0 <= target < V; any other target (-100, >= V) is ignored: lse 0, no loss,

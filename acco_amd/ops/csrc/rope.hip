@@ -5,6 +5,8 @@
 // Forward:  y1 = x1*cos - x2*sin ; y2 = x2*cos + x1*sin   (x2 = x[d+D/2])
 // Backward: rotation by -theta:  dx1 = dy1*cos + dy2*sin ;
 //           dx2 = dy2*cos - dy1*sin.
+// Also home of the KV-cache append of generation (kv_append_kernel), which
+// rotates K at its absolute position with the same rot8.
 
 #include "common.h"
 #include "kernels.h"
@@ -109,7 +111,83 @@ void rope_qk_inplace_kernel(u16* __restrict__ qkv,
   *reinterpret_cast<uint4*>(p2) = v2;
 }
 
+// KV-cache append: T new tokens per sequence from the projection's natural
+// layout (q / k / v base pointers with a row stride each, so the packed
+// q|k|v or k|v|q output and separate tensors are read in place) into the
+// caches [B, Hkv, Smax, D]. Token t of sequence b goes to cache row
+// p = clamp(cache_len[b], 0, Smax) + t; a row at or beyond Smax is dropped.
+// cache_len is data: it is clamped, then only compared. With tables K is
+// rotated by row p of the table (rot8: the bits a full forward computes for
+// that position) and the rotated q goes to q_out [B, T, H, D]; a dropped
+// token's q takes the table's last row (p < rows otherwise: rows >= Smax).
+// Without tables K is copied and q is not touched (Hq = 0). One thread owns
+// 8 pairs of one head, as in rope_qk_inplace_kernel.
+__global__ __launch_bounds__(256)
+void kv_append_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
+                      const u16* __restrict__ v, u16* __restrict__ q_out,
+                      u16* __restrict__ k_cache, u16* __restrict__ v_cache,
+                      const int* __restrict__ cache_len,
+                      const float* __restrict__ cos_t,
+                      const float* __restrict__ sin_t, unsigned total,
+                      unsigned T, unsigned Hq, unsigned Hkv, unsigned D,
+                      int Smax, int rows, long long q_rs, long long k_rs,
+                      long long v_rs) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= total) return;
+  const unsigned cph = D / 16;                  // 8-pair chunks per head
+  const unsigned ipt = (Hq + 2 * Hkv) * cph;    // items per token
+  const unsigned tok = i / ipt, r = i % ipt;
+  const unsigned b = tok / T, t = tok % T;
+  const unsigned hh = r / cph, c8 = (r % cph) * 8;
+  const int len = min(max(cache_len[b], 0), Smax);
+  const long long p = (long long)len + t;       // absolute position
+  const bool is_q = hh < Hq, is_k = !is_q && hh < Hq + Hkv;
+  if (!is_q && p >= Smax) return;               // dropped, never written
+  const unsigned h = is_q ? hh : (is_k ? hh - Hq : hh - Hq - Hkv);
+  const u16* src = is_q ? q + (long long)tok * q_rs
+                 : is_k ? k + (long long)tok * k_rs
+                        : v + (long long)tok * v_rs;
+  src += (long long)h * D + c8;
+  uint4 v1 = *reinterpret_cast<const uint4*>(src);
+  uint4 v2 = *reinterpret_cast<const uint4*>(src + D / 2);
+  if (cos_t != nullptr && (is_q || is_k)) {
+    const size_t row = (size_t)min(p, (long long)rows - 1);
+    const float4* cp = reinterpret_cast<const float4*>(cos_t + row * D + c8);
+    const float4* sp = reinterpret_cast<const float4*>(sin_t + row * D + c8);
+    const float4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
+    const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    rot8(v1, v2, cc, ss);
+  }
+  u16* dst = is_q ? q_out + ((long long)tok * Hq + h) * D
+                  : (is_k ? k_cache : v_cache) +
+                        (((long long)b * Hkv + h) * Smax + p) * D;
+  dst += c8;
+  *reinterpret_cast<uint4*>(dst) = v1;
+  *reinterpret_cast<uint4*>(dst + D / 2) = v2;
+}
+
 }  // namespace
+
+extern "C" void acco_kv_append(const void* q, const void* k, const void* v,
+                               void* q_out, void* k_cache, void* v_cache,
+                               const int* cache_len, const float* cos_t,
+                               const float* sin_t, int B, int T, int H,
+                               int Hkv, int D, int Smax, int table_rows,
+                               long long q_rs, long long k_rs, long long v_rs,
+                               hipStream_t stream) {
+  // q is read and written only with tables; without them it is the caller's
+  const int Hq = (cos_t != nullptr && q != nullptr) ? H : 0;
+  const unsigned total = (unsigned)((long long)B * T * (Hq + 2 * Hkv) *
+                                    (D / 16));
+  if (total == 0) return;
+  hipLaunchKernelGGL(kv_append_kernel, dim3((total + 255) / 256), dim3(256),
+                     0, stream, (const u16*)q, (const u16*)k, (const u16*)v,
+                     (u16*)q_out, (u16*)k_cache, (u16*)v_cache, cache_len,
+                     cos_t, sin_t, total, (unsigned)T, (unsigned)Hq,
+                     (unsigned)Hkv, (unsigned)D, Smax, table_rows, q_rs, k_rs,
+                     v_rs);
+}
 
 extern "C" void acco_rope_qk_inplace(void* qkv, const float* cos_t,
                                      const float* sin_t, long long T, int S,

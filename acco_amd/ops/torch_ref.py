@@ -21,7 +21,8 @@ def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
     """RMSNorm (Llama-family; replaces HF modeling_llama RMSNorm inside K1,
     reference trainer_decoupled.py:26-34 forward)."""
     dt = x.dtype
-    xf = x.float()
+    # fp32 math for bf16 / fp32 inputs; a double model stays in double
+    xf = x.to(torch.promote_types(dt, torch.float32))
     var = xf.pow(2).mean(-1, keepdim=True)
     return (xf * torch.rsqrt(var + eps)).to(dt) * weight
 
@@ -132,7 +133,9 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         v = v.repeat_interleave(rep, dim=1)
     if scale is None:
         scale = 1.0 / math.sqrt(D)
-    scores = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+    # fp32 math for bf16 / fp32 inputs; a double model stays in double
+    wide = torch.promote_types(q.dtype, torch.float32)
+    scores = torch.matmul(q.to(wide), k.to(wide).transpose(-1, -2)) * scale
     idx = torch.arange(S, device=q.device)
     mask = idx[None, :] > idx[:, None]           # future → masked
     if window is not None:
@@ -142,8 +145,89 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         mask = mask[None, None] | (idx[None, None, None, :] < lo[:, None, :, None])
     scores = scores.masked_fill(mask, float("-inf"))
     probs = torch.softmax(scores, dim=-1)
-    out = torch.matmul(probs, v.float()).to(q.dtype)
+    out = torch.matmul(probs, v.to(wide)).to(q.dtype)
     return out.transpose(1, 2)
+
+
+# ------------------------------------------------- KV cache (generation)
+# k_cache / v_cache [B, Hkv, Smax, D] per layer, K stored after RoPE;
+# cache_len int [B] = tokens already cached per sequence (ragged batches).
+# cache_len is data: it is clamped into [0, Smax] and otherwise only
+# compared, the convention of the document-mask arrays. No host sync.
+
+@torch.no_grad()
+def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
+              cache_len: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+              q: Optional[torch.Tensor] = None,
+              cos: Optional[torch.Tensor] = None,
+              sin: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Write k, v [B, T, Hkv, D] of T new tokens per sequence into the caches,
+    in place: token t of sequence b goes to row p = clamp(cache_len[b]) + t,
+    and a row at or beyond Smax is dropped. With `cos` / `sin` ([>= Smax, D])
+    K is rotated by row p, its absolute position, exactly as rope_apply
+    rotates it in a full forward, and the rotated q [B, T, H, D] is returned
+    (a dropped token's q takes the table's last row); without them K is copied
+    and None is returned. `cache_len` is not modified."""
+    B, T, Hkv, D = k.shape
+    Smax = k_cache.shape[2]
+    base = cache_len.long().clamp(0, Smax)                      # [B]
+    q_rot = None
+    if cos is not None:
+        pos = base[:, None] + torch.arange(T, device=k.device)  # [B, T]
+        rows = pos.clamp(max=cos.shape[0] - 1)
+        c = cos[rows].to(k.dtype)[:, :, None, :]
+        s = sin[rows].to(k.dtype)[:, :, None, :]
+        k = k * c + _rotate_half(k) * s
+        q_rot = q * c + _rotate_half(q) * s
+    if T == 0:
+        return q_rot
+    # gather form (row r of the cache takes token r - base when there is
+    # one): deterministic, nothing indexes past either tensor
+    t = torch.arange(Smax, device=k.device)[None, :] - base[:, None]
+    take = ((t >= 0) & (t < T))[:, None, :, None]               # [B,1,Smax,1]
+    idx = t.clamp(0, T - 1)[:, None, :, None].expand(B, Hkv, Smax, D)
+    for cache, new in ((k_cache, k), (v_cache, v)):
+        rows = new.permute(0, 2, 1, 3).gather(2, idx).to(cache.dtype)
+        cache.copy_(torch.where(take, rows, cache))
+    return q_rot
+
+
+def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, cache_len: torch.Tensor,
+                     scale: Optional[float] = None,
+                     window: Optional[int] = None) -> torch.Tensor:
+    """Attention of one query token per sequence against the cache.
+
+    q [B, H, D] is the query of the LAST cached token, position L - 1 with
+    L = clamp(cache_len[b], 0, Smax); it attends keys [max(0, L - window), L)
+    (`window` None or 0 = no window; the convention of causal_attention:
+    j > L - 1 - window). Rows at or beyond L are never used, whatever they
+    hold. L = 0 gives zeros. Math in the wider of q's dtype and fp32; returns
+    [B, H, D] in q's dtype."""
+    B, H, D = q.shape
+    Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
+    wide = torch.promote_types(q.dtype, torch.float32)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    L = cache_len.long().clamp(0, Smax)[:, None]                # [B, 1]
+    j = torch.arange(Smax, device=q.device)[None, :]
+    allow = j < L
+    if window:
+        allow = allow & (j >= L - int(window))
+    a4 = allow[:, None, :, None]
+    zero = torch.zeros((), dtype=wide, device=q.device)
+    k = torch.where(a4, k_cache.to(wide), zero)
+    v = torch.where(a4, v_cache.to(wide), zero)
+    if Hkv != H:
+        k = k.repeat_interleave(H // Hkv, dim=1)
+        v = v.repeat_interleave(H // Hkv, dim=1)
+    s = torch.einsum("bhd,bhjd->bhj", q.to(wide), k) * scale
+    s = s.masked_fill(~allow[:, None, :], float("-inf"))
+    m = s.amax(-1, keepdim=True).clamp(min=torch.finfo(wide).min)
+    p = torch.exp(s - m)                                        # masked: 0
+    l = p.sum(-1, keepdim=True)
+    o = torch.einsum("bhj,bhjd->bhd", p, v)
+    return (o / l.clamp(min=torch.finfo(wide).tiny)).to(q.dtype)
 
 
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,

@@ -1,14 +1,17 @@
 """Sample text from a trained checkpoint (sanity/demo tool).
 
-Greedy or temperature sampling with a full-context re-forward per token
-(the models are training-shaped — no KV cache; fine for short demos).
-Beyond the reference's surface (it has no generation path); useful for
-eyeballing that a checkpoint learned anything.
+Greedy or temperature sampling. By default every new token re-forwards the
+whole context (sliding over the last max_position_embeddings tokens); with
+--kv-cache the prompt is prefilled once into a KV cache and every new token
+is one single-token decode step on it (models/kv_cache.py), which needs
+prompt + max-new <= max_position_embeddings. Both paths share the sampling
+code and the seeded generator. Beyond the reference's surface (it has no
+generation path); useful for judging what a checkpoint learned.
 
 Usage (config overrides use the same syntax as main.py):
   python tools/generate.py --ckpt checkpoints/<id>_model.pt \\
       --tokenizer corpus/tokenizer --prompt "the" --max-new 64 \\
-      --temperature 0.8 model=gptneo [model.hidden_size=... ...]
+      --temperature 0.8 [--kv-cache] model=gptneo [model.hidden_size=... ...]
 """
 
 from __future__ import annotations
@@ -22,21 +25,51 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _sample(step: torch.Tensor, temperature: float,
+            gen: torch.Generator) -> torch.Tensor:
+    """Next token [B, 1] from the last position's logits [B, V] (on the CPU)."""
+    if temperature <= 0:
+        return step.argmax(-1, keepdim=True)
+    probs = torch.softmax(step / temperature, dim=-1)
+    return torch.multinomial(probs, 1, generator=gen)
+
+
 @torch.no_grad()
 def generate(model, ids: torch.Tensor, max_new: int, temperature: float,
-             max_len: int, seed: int = 0) -> torch.Tensor:
+             max_len: int, seed: int = 0,
+             use_cache: bool = False) -> torch.Tensor:
     gen = torch.Generator(device="cpu").manual_seed(seed)
     model.eval()
+    if use_cache:
+        return _generate_cached(model, ids, max_new, temperature, max_len,
+                                gen)
     for _ in range(max_new):
         out = model(ids[:, -max_len:])
         logits = out[0] if isinstance(out, tuple) else out
-        step = logits[:, -1, :].float().cpu()
-        if temperature <= 0:
-            nxt = step.argmax(-1, keepdim=True)
-        else:
-            probs = torch.softmax(step / temperature, dim=-1)
-            nxt = torch.multinomial(probs, 1, generator=gen)
+        nxt = _sample(logits[:, -1, :].float().cpu(), temperature, gen)
         ids = torch.cat([ids, nxt.to(ids.device)], dim=1)
+    return ids
+
+
+def _generate_cached(model, ids, max_new, temperature, max_len, gen):
+    """One prefill, then one decode_step per token; there is no sliding
+    window over the context here, so it all has to fit."""
+    from acco_amd.models.kv_cache import KVCache
+    total = ids.shape[1] + max_new
+    if total > max_len:
+        raise ValueError(
+            f"--kv-cache needs prompt + max-new <= max_position_embeddings: "
+            f"{ids.shape[1]} + {max_new} > {max_len} (the uncached path "
+            "slides over the context instead)")
+    if max_new <= 0:
+        return ids
+    cache = KVCache.allocate(model, ids.shape[0], total)
+    logits = model.prefill(ids, None, cache)
+    for i in range(max_new):
+        nxt = _sample(logits.float().cpu(), temperature, gen).to(ids.device)
+        ids = torch.cat([ids, nxt], dim=1)
+        if i + 1 < max_new:
+            logits = model.decode_step(nxt[:, 0], cache)
     return ids
 
 
@@ -50,6 +83,10 @@ def main(argv=None) -> str:
     ap.add_argument("--max-new", type=int, default=64)
     ap.add_argument("--temperature", type=float, default=0.8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--kv-cache", action="store_true",
+                    help="prefill once, then one cached decode step per "
+                         "token (needs prompt + max-new <= "
+                         "max_position_embeddings)")
     ap.add_argument("overrides", nargs="*",
                     help="config overrides, e.g. model=gptneo")
     args = ap.parse_args(argv)
@@ -70,7 +107,7 @@ def main(argv=None) -> str:
     ids = torch.tensor([tok.encode(args.prompt).ids], device=device)
     max_len = int(model.cfg.max_position_embeddings)
     out = generate(model, ids, args.max_new, args.temperature, max_len,
-                   seed=args.seed)
+                   seed=args.seed, use_cache=args.kv_cache)
     text = tok.decode(out[0].tolist())
     print(text)
     return text
