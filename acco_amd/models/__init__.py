@@ -6,11 +6,12 @@ from __future__ import annotations
 import os
 
 from acco_amd.models.config import GPTNeoConfig, LlamaConfig
+from acco_amd.models.generation import generate
 from acco_amd.models.gptneo import GPTNeoForCausalLM
 from acco_amd.models.llama import LlamaForCausalLM
 
-__all__ = ["build_model", "load_pretrained", "GPTNeoConfig", "LlamaConfig",
-           "GPTNeoForCausalLM", "LlamaForCausalLM"]
+__all__ = ["build_model", "load_pretrained", "generate", "GPTNeoConfig",
+           "LlamaConfig", "GPTNeoForCausalLM", "LlamaForCausalLM"]
 
 
 def build_model(model_cfg, vocab_size_override=None):

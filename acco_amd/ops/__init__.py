@@ -275,6 +275,32 @@ def decode_attention_splits(bhkv: int, smax: int) -> Tuple[int, int]:
     return int(n_split), int(chunk)
 
 
+def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
+                  top_p: float = 1.0, seed: int, step: int,
+                  done: Optional[torch.Tensor] = None, eos_id: int = -1
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                             torch.Tensor]:
+    """One token per row of logits [B, V], drawn on the logits' device:
+    (token int64 [B] in [0, V), logprob fp32 [B], thr bf16 [B], n_kept int32
+    [B]). temperature > 0: top-k (0 = off), then top-p (>= 1 = off), then a
+    Gumbel-max draw from a counter-based generator keyed by (seed, step, row,
+    index): a pure function of its arguments, bitwise reproducible.
+    temperature == 0: the argmax. `done` (uint8 [B], updated in place) with
+    0 <= eos_id < V pins finished rows to eos_id (torch_ref.sample_logits has
+    the semantics). The caller counts `step`; nothing is read from the device.
+    One HIP kernel for bf16 on the GPU; the fp64 reference for CPU tensors,
+    other dtypes and ACCO_FORCE_REF=1."""
+    if _use_ref(logits) or logits.dtype != torch.bfloat16:
+        return torch_ref.sample_logits(
+            logits, temperature=temperature, top_k=top_k, top_p=top_p,
+            seed=seed, step=step, done=done, eos_id=eos_id)
+    mask = (1 << 64) - 1
+    token, logprob, thr, n_kept = hip_ext().sample_logits(
+        logits, float(temperature), int(top_k), float(top_p),
+        int(seed) & mask, int(step) & mask, done, int(eos_id))
+    return token, logprob, thr, n_kept
+
+
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     if _use_ref(logits, "ce_fwd"):
         return torch_ref.causal_lm_loss(logits, labels)

@@ -1149,9 +1149,76 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
   return o;
 }
 
+// ---- on-device sampling (sample.hip)
+// (token int64 [B], logprob fp32 [B], thr bf16 [B], n_kept int32 [B]) of one
+// draw per row. The argument contract: logits CUDA bf16 [B, V] whose last dim
+// is contiguous and whose rows lie stride(0) >= V elements apart (no
+// alignment asked: the kernel splits each row by its own address),
+// 1 <= V < 2^31, B < 2^31; temperature finite and >= 0 (0 = greedy);
+// top_k >= 0 (0 = off); top_p > 0 (>= 1 = off); done, when given, contiguous
+// uint8 [B] on the logits' device, updated in place, and then
+// 0 <= eos_id < V (a finished row's token is eos_id, and every token must
+// index the embedding).
+std::vector<at::Tensor> sample_logits(at::Tensor logits, double temperature,
+                                      int64_t top_k, double top_p,
+                                      uint64_t seed, uint64_t step,
+                                      c10::optional<at::Tensor> done,
+                                      int64_t eos_id) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16,
+              "logits must be CUDA bf16, got ", logits.scalar_type(), " on ",
+              logits.device());
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1 &&
+              logits.size(1) < (1LL << 31) && logits.size(0) < (1LL << 31),
+              "logits must be [B, V] with 1 <= V < 2^31 and B < 2^31, got ",
+              logits.sizes());
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V == 1 || logits.stride(1) == 1,
+              "logits: the last dim must be contiguous, got strides ",
+              logits.strides());
+  const int64_t rs = B > 1 ? logits.stride(0) : V;
+  TORCH_CHECK(rs >= V, "logits: rows must not overlap (row stride >= V = ", V,
+              "), got strides ", logits.strides());
+  TORCH_CHECK(temperature >= 0.0 && temperature < 1e30,
+              "temperature must be finite and >= 0, got ", temperature);
+  TORCH_CHECK(temperature == 0.0 || (float)temperature > 0.0f,
+              "temperature underflows fp32: ", temperature);
+  TORCH_CHECK(top_k >= 0, "top_k must be >= 0 (0 = off), got ", top_k);
+  TORCH_CHECK(top_p > 0.0, "top_p must be > 0 (>= 1 = off), got ", top_p);
+  unsigned char* done_ptr = nullptr;
+  if (done.has_value()) {
+    TORCH_CHECK(done->is_cuda() && done->device() == logits.device() &&
+                done->scalar_type() == at::kByte && done->is_contiguous() &&
+                done->dim() == 1 && done->size(0) == B,
+                "done must be contiguous uint8 [B] = [", B, "] on ",
+                logits.device(), ", got ", done->scalar_type(), " ",
+                done->sizes(), " on ", done->device());
+    TORCH_CHECK(eos_id >= 0 && eos_id < V, "with done, eos_id must be in "
+                "[0, V = ", V, "), got ", eos_id);
+    done_ptr = done->data_ptr<unsigned char>();
+  }
+  auto opts = logits.options();
+  auto token = at::empty({B}, opts.dtype(at::kLong));
+  auto logprob = at::empty({B}, opts.dtype(at::kFloat));
+  auto thr = at::empty({B}, opts);
+  auto n_kept = at::empty({B}, opts.dtype(at::kInt));
+  if (B == 0) return {token, logprob, thr, n_kept};
+  acco_sample_logits(logits.data_ptr(), rs, (int)B, (int)V,
+                     (float)temperature, (int)(top_k < V ? top_k : V), top_p,
+                     seed, step, done_ptr, eos_id,
+                     reinterpret_cast<long long*>(token.data_ptr<int64_t>()),
+                     logprob.data_ptr<float>(), thr.data_ptr(),
+                     n_kept.data_ptr<int>(), cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {token, logprob, thr, n_kept};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("sample_logits", &sample_logits, py::arg("logits"),
+        py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("seed"), py::arg("step"), py::arg("done"),
+        py::arg("eos_id"));
   m.def("kv_append", &kv_append, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("cos"), py::arg("sin"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("cache_len"));

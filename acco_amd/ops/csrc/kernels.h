@@ -121,6 +121,22 @@ void acco_ce_rows_bwd(void* logits_inout, const long long* targets,
                       const float* lse, const float* scale_dev, long long T,
                       int V, float epsilon, hipStream_t s);
 
+// ---- sample.hip
+// One token per row of bf16 logits [B, V] (rows row_stride elements apart,
+// any alignment): temperature, top-k (0 = off, ties at the threshold kept),
+// top-p (>= 1 = off, on the top-k survivors) and a Gumbel-max draw keyed by
+// (seed, step, row, index); temperature == 0 is the argmax and ignores the
+// filters. Outputs by ordinary stores: token int64 [B] in [0, V), logprob
+// fp32 [B], thr bf16 [B], n_kept int32 [B]. done (uint8 [B], nullable): a set
+// flag makes the row's token eos_id (in [0, V)) with nothing drawn, otherwise
+// done[b] = (token == eos_id). One workgroup per row, bitwise reproducible.
+void acco_sample_logits(const void* logits, long long row_stride, int B,
+                        int V, float temperature, int top_k, double top_p,
+                        unsigned long long seed, unsigned long long step,
+                        unsigned char* done, long long eos_id,
+                        long long* token, float* logprob, void* thr,
+                        int* n_kept, hipStream_t s);
+
 // ---- gemm_nt.hip
 void acco_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K,
                   hipStream_t stream);

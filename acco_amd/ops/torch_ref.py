@@ -230,6 +230,217 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return (o / l.clamp(min=torch.finfo(wide).tiny)).to(q.dtype)
 
 
+# ------------------------------------------------- sampling (generation)
+# The executable definition of ops.sample_logits (kernel: csrc/sample.hip).
+# Integer parts (keys, thresholds, the generator) are exact; every real
+# quantity is fp64.
+
+SAMPLE_KEY_MIN = 0x0080          # key of the lowest finite bf16
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 (Salmon et al., SC'11): ctr = four and key = two uint32
+    values or equal-shaped arrays of them; returns the four output words as
+    numpy uint64 arrays holding uint32 values."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(x, dtype=np.uint64) & m32 for x in ctr]
+    k = [np.asarray(x, dtype=np.uint64) & m32 for x in key]
+    s32 = np.uint64(32)
+    for r in range(10):
+        if r:
+            k = [(k[0] + np.uint64(_PHILOX_W0)) & m32,
+                 (k[1] + np.uint64(_PHILOX_W1)) & m32]
+        p0 = np.uint64(_PHILOX_M0) * c[0]      # < 2^64: no wrap
+        p1 = np.uint64(_PHILOX_M1) * c[2]
+        c = [(p1 >> s32) ^ c[1] ^ k[0], p1 & m32,
+             (p0 >> s32) ^ c[3] ^ k[1], p0 & m32]
+    return c
+
+
+def sample_uniform(idx, row: int, step: int, seed: int):
+    """u_i = (r_i + 0.5) · 2^-23 in fp64 (exact in fp32 too, inside (0, 1)):
+    r_i = top 23 bits of word 0 of Philox4x32-10 at counter
+    (i, row, step_lo, step_hi) under key (seed_lo, seed_hi)."""
+    import numpy as np
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    idx = np.asarray(idx, dtype=np.uint64)
+    full = lambda v: np.full(idx.shape, v, dtype=np.uint64)   # noqa: E731
+    w0 = philox4x32_10(
+        (idx, full(row), full(step & 0xFFFFFFFF), full(step >> 32)),
+        (full(seed & 0xFFFFFFFF), full(seed >> 32)))[0]
+    r = (w0 >> np.uint64(9)).astype(np.float64)
+    return (r + 0.5) * 2.0 ** -23
+
+
+def sample_keys(bits):
+    """Order-preserving uint16 keys of bf16 bit patterns (numpy uint16 in,
+    int64 out): -0 -> +0, +-inf -> the largest finite bf16 of that sign, NaN
+    -> key 0, below every value."""
+    import numpy as np
+    b = bits.astype(np.int64) & 0xFFFF
+    mag = b & 0x7FFF
+    b = np.where(mag == 0x7F80, (b & 0x8000) | 0x7F7F, b)
+    b = np.where(mag == 0, 0, b)
+    key = np.where(b & 0x8000, ~b & 0xFFFF, b | 0x8000)
+    return np.where(mag > 0x7F80, 0, key)
+
+
+def sample_key_bits(key):
+    """The bf16 bit pattern of a key (inverse of sample_keys on values)."""
+    import numpy as np
+    key = np.asarray(key, dtype=np.int64)
+    return np.where(key & 0x8000, key ^ 0x8000, ~key & 0xFFFF)
+
+
+def _bf16_bits_to_f64(bits):
+    import numpy as np
+    return (np.asarray(bits, dtype=np.int64).astype(np.uint32)
+            << np.uint32(16)).view(np.float32).astype(np.float64)
+
+
+def sample_row(bits, row: int, temperature: float, top_k: int, top_p: float,
+               seed: int, step: int) -> dict:
+    """One row (numpy uint16 bf16 bit patterns [V]) of sample_logits, with
+    what the tests' preconditions need next to the four outputs:
+      p_margin  min over distinct values v of |mass(x >= v) / Z_k - top_p|
+                (inf with top-p off)
+      gap, gap_scale  best minus second-best perturbed score, and the larger
+                |x/T| + |g| + 1 of the two (gap inf with one candidate)
+      gap_pairwise  min over the other kept j of (score_best - score_j) /
+                (scale_best + scale_j), scale = |x/T| + |g| + 1
+      mean_abs_a  sum_i p_i · |x_i - max| / T over the top-k survivors
+      a_tok, log_z  logprob = a_tok - log_z
+    The temperature is taken as fp32 (the kernel's argument type)."""
+    import numpy as np
+    V = bits.shape[0]
+    key = sample_keys(bits)
+    valid = key > 0
+    out = dict(token=0, logprob=0.0, thr_bits=int(
+        sample_key_bits(SAMPLE_KEY_MIN)), n_kept=0, p_margin=math.inf,
+        gap=math.inf, gap_scale=1.0, gap_pairwise=math.inf, mean_abs_a=0.0,
+        a_tok=0.0, log_z=0.0)
+    if not valid.any():
+        return out
+    x = _bf16_bits_to_f64(sample_key_bits(key))        # sanitised values
+    greedy = float(temperature) == 0.0
+    T = 1.0 if greedy else float(np.float32(temperature))
+    kmax = key.max()
+    a = (x - x[key == kmax][0]) / T                    # <= 0 where valid
+    thr = SAMPLE_KEY_MIN
+    if not greedy and 1 <= top_k < V:
+        thr = max(thr, int(np.sort(key)[V - top_k]))   # k-th largest
+    w = np.where(key >= thr, np.exp(np.where(valid, a, 0.0)), 0.0)
+    z_k = w.sum()
+    out["mean_abs_a"] = float((w * np.abs(np.where(valid, a, 0.0))).sum()
+                              / z_k)
+    if not greedy and top_p < 1.0:
+        order = np.argsort(-key, kind="stable")
+        ks, cw = key[order], np.cumsum(w[order])
+        last = np.ones(V, dtype=bool)
+        last[:-1] = ks[:-1] != ks[1:]                  # end of a tie group
+        cand = last & (ks >= thr)
+        frac = cw[cand] / z_k                          # mass(x >= v) / Z_k
+        out["p_margin"] = float(np.abs(frac - top_p).min())
+        hit = np.nonzero(frac >= top_p)[0]
+        # the first group that reaches top_p; rounding may leave none
+        thr_p = int(ks[cand][hit[0]]) if hit.size else thr
+        thr = max(thr, thr_p)
+    kept = key >= thr
+    idx = np.nonzero(kept)[0]
+    if greedy:
+        score = x[idx]
+        g = np.zeros(idx.shape)
+    else:
+        u = sample_uniform(idx, row, step, seed)
+        g = -np.log(-np.log(u))
+        score = x[idx] / T + g
+    j = int(np.argmax(score))                          # lowest index on ties
+    tok = int(idx[j])
+    if idx.size > 1:
+        rest = np.delete(score, j)
+        j2 = int(np.argmax(rest))
+        j2 += j2 >= j
+        out["gap"] = float(score[j] - score[j2])
+        scale = np.abs(x[idx] / T) + np.abs(g) + 1.0
+        out["gap_scale"] = float(max(scale[j], scale[j2]))
+        pair = (score[j] - score) / (scale[j] + scale)
+        pair[j] = np.inf
+        out["gap_pairwise"] = float(pair.min())
+    z = w[kept].sum()
+    out.update(token=tok, a_tok=float(a[tok]), log_z=float(np.log(z)),
+               logprob=float(a[tok] - np.log(z)),
+               thr_bits=int(sample_key_bits(thr)), n_kept=int(idx.size))
+    return out
+
+
+def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
+                  top_p: float = 1.0, seed: int, step: int,
+                  done: Optional[torch.Tensor] = None, eos_id: int = -1,
+                  details: Optional[list] = None):
+    """(token int64 [B], logprob fp32 [B], thr bf16 [B], n_kept int32 [B]) of
+    one draw per row of logits [B, V], taken as bf16 (another dtype is
+    rounded to it first: thresholds are keys of the bf16 value).
+
+    temperature > 0: top-k (0 = off; x >= the k-th largest value, ties kept),
+    then top-p (>= 1 = off) on softmax(x / T) renormalised over the top-k
+    survivors (the largest value whose upper mass reaches top_p; ties kept,
+    at least one token), then Gumbel-max token = argmax_i x_i / T + g_i over
+    the kept i, lowest index on ties, g_i from sample_uniform(i, b, step,
+    seed). temperature == 0: the argmax, filters ignored. logprob: log of the
+    token's probability in the filtered, temperature-scaled distribution
+    (greedy: the unfiltered T = 1 softmax). A row without a finite logit
+    gives token 0, logprob 0, n_kept 0.
+
+    done (uint8 [B], updated in place) with 0 <= eos_id < V: a set flag makes
+    the row's token eos_id, nothing is drawn (logprob 0, thr 0, n_kept 0);
+    otherwise done[b] |= token == eos_id. `details`, a list, receives
+    sample_row's dict of every row that was drawn."""
+    import numpy as np
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"logits must be [B, V >= 1], got {logits.shape}")
+    if not (0.0 <= float(temperature) < 1e30):
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    if int(top_k) < 0 or not float(top_p) > 0.0:
+        raise ValueError(f"need top_k >= 0 and top_p > 0, got {top_k}, "
+                         f"{top_p}")
+    B, V = logits.shape
+    if done is not None and not 0 <= int(eos_id) < V:
+        raise ValueError(f"with done, eos_id must be in [0, {V}), got "
+                         f"{eos_id}")
+    dev = logits.device
+    bits = logits.detach().to(device="cpu", dtype=torch.bfloat16) \
+        .contiguous().view(torch.int16).numpy().view(np.uint16)
+    done_np = None
+    if done is not None:
+        done_np = done.detach().to("cpu").numpy()      # shared when on CPU
+    token = np.zeros(B, dtype=np.int64)
+    logprob = np.zeros(B, dtype=np.float32)
+    thr = np.zeros(B, dtype=np.int16)
+    n_kept = np.zeros(B, dtype=np.int32)
+    for b in range(B):
+        if done_np is not None and done_np[b]:
+            token[b] = int(eos_id)
+            continue
+        r = sample_row(bits[b], b, float(temperature), int(top_k),
+                       float(top_p), seed, step)
+        if details is not None:
+            details.append(r)
+        token[b], logprob[b], n_kept[b] = r["token"], r["logprob"], \
+            r["n_kept"]
+        thr[b] = np.uint16(r["thr_bits"]).view(np.int16)
+        if done_np is not None:
+            done_np[b] = r["token"] == int(eos_id)
+    if done is not None and done.device.type != "cpu":
+        done.copy_(torch.from_numpy(done_np))
+    return (torch.from_numpy(token).to(dev),
+            torch.from_numpy(logprob).to(dev),
+            torch.from_numpy(thr).view(torch.bfloat16).to(dev),
+            torch.from_numpy(n_kept).to(dev))
+
+
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,
                    ignore_index: int = -100) -> torch.Tensor:
     """Shifted causal-LM cross entropy (HF CausalLM loss inside K1/K9)."""

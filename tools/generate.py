@@ -5,13 +5,18 @@ whole context (sliding over the last max_position_embeddings tokens); with
 --kv-cache the prompt is prefilled once into a KV cache and every new token
 is one single-token decode step on it (models/kv_cache.py), which needs
 prompt + max-new <= max_position_embeddings. Both paths share the sampling
-code and the seeded generator. Beyond the reference's surface (it has no
+code and the seeded generator, which run on the CPU: the logits are copied to
+the host every token. --device-sampling (implies --kv-cache) runs
+acco_amd.models.generate instead: top-k / top-p and the draw happen on the
+model's device from a counter-based generator, so the same --seed gives other
+tokens than the CPU paths. Beyond the reference's surface (it has no
 generation path); useful for judging what a checkpoint learned.
 
 Usage (config overrides use the same syntax as main.py):
   python tools/generate.py --ckpt checkpoints/<id>_model.pt \\
       --tokenizer corpus/tokenizer --prompt "the" --max-new 64 \\
       --temperature 0.8 [--kv-cache] model=gptneo [model.hidden_size=... ...]
+  ... --device-sampling --top-k 50 --top-p 0.9 ...
 """
 
 from __future__ import annotations
@@ -87,9 +92,23 @@ def main(argv=None) -> str:
                     help="prefill once, then one cached decode step per "
                          "token (needs prompt + max-new <= "
                          "max_position_embeddings)")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="sample on the model's device with "
+                         "acco_amd.models.generate (implies --kv-cache): no "
+                         "copy of the logits to the host per token; draws "
+                         "come from its own seeded generator, not the CPU one")
+    ap.add_argument("--top-k", type=int, default=0,
+                    help="keep the k largest logits (0 = off; needs "
+                         "--device-sampling)")
+    ap.add_argument("--top-p", type=float, default=1.0,
+                    help="nucleus mass (>= 1 = off; needs --device-sampling)")
     ap.add_argument("overrides", nargs="*",
                     help="config overrides, e.g. model=gptneo")
     args = ap.parse_args(argv)
+    if args.top_k < 0 or not args.top_p > 0:
+        ap.error("need --top-k >= 0 and --top-p > 0")
+    if (args.top_k != 0 or args.top_p < 1.0) and not args.device_sampling:
+        ap.error("--top-k / --top-p need --device-sampling")
 
     from acco_amd.config import load_config
     from acco_amd.models import build_model, load_pretrained
@@ -106,8 +125,18 @@ def main(argv=None) -> str:
 
     ids = torch.tensor([tok.encode(args.prompt).ids], device=device)
     max_len = int(model.cfg.max_position_embeddings)
-    out = generate(model, ids, args.max_new, args.temperature, max_len,
-                   seed=args.seed, use_cache=args.kv_cache)
+    if args.device_sampling:
+        from acco_amd.models import generate as generate_on_device
+        model.eval()
+        # stops at the model config's eos_token_id, if it has one
+        out, n_new = generate_on_device(
+            model, ids, max_new=max(args.max_new, 0),
+            temperature=max(args.temperature, 0.0), top_k=args.top_k,
+            top_p=args.top_p, seed=args.seed)
+        out = out[:, :ids.shape[1] + int(n_new[0])]
+    else:
+        out = generate(model, ids, args.max_new, args.temperature, max_len,
+                       seed=args.seed, use_cache=args.kv_cache)
     text = tok.decode(out[0].tolist())
     print(text)
     return text
