@@ -13,15 +13,15 @@ from typing import Optional, Tuple
 import torch
 
 from acco_amd import ops
-from acco_amd.models.kv_cache import KVCache
+from acco_amd.models.kv_cache import KVCache, prefill_chunked
 
 
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor,
              lens: Optional[torch.Tensor] = None, *, max_new: int,
              temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
-             seed: int = 0, eos_token_id: Optional[int] = None
-             ) -> Tuple[torch.Tensor, torch.Tensor]:
+             seed: int = 0, eos_token_id: Optional[int] = None,
+             prefill_chunk: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """(tokens int64 [B, S + max_new], n_generated int64 [B]) for prompts
     `input_ids` [B, S] of `model` (LlamaForCausalLM or GPTNeoForCausalLM, in
     eval mode). Sequence b holds lens[b] <= S prompt tokens (None = all S),
@@ -33,7 +33,10 @@ def generate(model, input_ids: torch.Tensor,
     as the generator's counter, so the same arguments give the same tokens;
     temperature 0 is greedy. eos_token_id (default: model.cfg.eos_token_id;
     None = never stop): once sequence b draws it, b emits it from then on;
-    n_generated[b] counts b's tokens up to and including its first eos."""
+    n_generated[b] counts b's tokens up to and including its first eos.
+    prefill_chunk (0 < prefill_chunk < S): the prompt goes through the cache
+    in slices of that many columns (kv_cache.prefill_chunked), which bounds
+    the prefill's activation memory; 0 = one prefill of the whole prompt."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B, S], got {input_ids.shape}")
     B, S = input_ids.shape
@@ -68,7 +71,10 @@ def generate(model, input_ids: torch.Tensor,
     if eos_token_id is not None:
         done = torch.zeros(B, device=dev, dtype=torch.uint8)
     cache = KVCache.allocate(model, B, total)
-    logits = model.prefill(input_ids, lens, cache)
+    if 0 < int(prefill_chunk) < S:
+        logits = prefill_chunked(model, input_ids, lens, cache, prefill_chunk)
+    else:
+        logits = model.prefill(input_ids, lens, cache)
     for i in range(max_new):
         if done is None:
             n_generated += 1

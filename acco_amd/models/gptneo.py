@@ -22,7 +22,7 @@ import torch.nn as nn
 from acco_amd import ops
 from acco_amd.models.fuse import arena_linear, arena_lm_loss
 from acco_amd.models.config import GPTNeoConfig
-from acco_amd.models.kv_cache import prefill
+from acco_amd.models.kv_cache import extend, prefill
 
 
 class GPTNeoSelfAttention(nn.Module):
@@ -104,6 +104,24 @@ class GPTNeoSelfAttention(nn.Module):
         o = ops.decode_attention(q, kc, vc, lens1, scale=1.0, window=window)
         return arena_linear(self.out_proj, o.reshape(B, 1, -1))
 
+    def extend(self, x: torch.Tensor, cache, layer: int) -> torch.Tensor:
+        """T tokens per sequence, x [B, T, hidden]: project, append K and V
+        to layer `layer` of the cache at cache.lens[b] + t, attend everything
+        cached up to each token's own position (the last window_size of it in
+        a local layer)."""
+        B, T, _ = x.shape
+        H, hd = self.cfg.num_heads, self.cfg.head_dim
+        q = self.q_proj(x).view(B, T, H, hd)
+        k = self.k_proj(x).view(B, T, H, hd)
+        v = self.v_proj(x).view(B, T, H, hd)
+        kc, vc = cache.k[layer], cache.v[layer]
+        ops.kv_append(kc, vc, cache.lens, k, v)
+        window = (self.cfg.window_size
+                  if self.attention_type == "local" else None)
+        o = ops.extend_attention(q, kc, vc, cache.lens, scale=1.0,
+                                 window=window)
+        return arena_linear(self.out_proj, o.reshape(B, T, -1))
+
 
 class GPTNeoAttention(nn.Module):
     """Wrapper level kept so state_dict keys read attn.attention.* like HF."""
@@ -137,17 +155,20 @@ class GPTNeoBlock(nn.Module):
         self.mlp = GPTNeoMLP(cfg)
 
     def forward(self, pending, residual, doc_start=None, doc_end=None,
-                kv=None, decode=None):
+                kv=None, decode=None, extend=None):
         """(pending, residual) form — every residual add fused into the
         following LayerNorm kernel (see LlamaDecoderLayer); returns the
         un-added MLP output + running residual, ln_f completes the last add.
         `kv` (prefill) is handed to the attention; `decode` = (cache, layer
-        index, lens + 1) makes this a single-token step on the cache. Both
-        None: the training forward."""
+        index, lens + 1) makes this a single-token step on the cache, `extend`
+        = (cache, layer index) a multi-token one. All None: the training
+        forward."""
         h1, residual = ops.add_layer_norm(pending, residual, self.ln_1.weight,
                                           self.ln_1.bias, self.ln_1.eps)
         if decode is not None:
             a = self.attn.attention.decode(h1, *decode)
+        elif extend is not None:
+            a = self.attn.attention.extend(h1, *extend)
         elif kv is not None:
             a = self.attn(h1, doc_start, doc_end, kv)
         else:
@@ -228,6 +249,25 @@ class GPTNeoModel(nn.Module):
         cache.lens = lens1
         return y[:, 0]
 
+    def extend(self, tokens: torch.Tensor, cache,
+               n_new: torch.Tensor) -> torch.Tensor:
+        """Hidden states [B, T, hidden] of T new tokens per sequence at
+        positions cache.lens[b] + t (wpe is read there, clamped into the
+        table); appends to every layer of the cache and advances cache.lens
+        by n_new (int32 [B]) once, after the last layer."""
+        T = tokens.shape[1]
+        pos = (cache.lens.long()[:, None]
+               + torch.arange(T, device=tokens.device)[None, :])
+        pos = pos.clamp(0, self.wpe.num_embeddings - 1)
+        pending = self.wte(tokens) + self.wpe(pos)
+        residual = None
+        for i, block in enumerate(self.h):
+            pending, residual = block(pending, residual, extend=(cache, i))
+        y, _ = ops.add_layer_norm(pending, residual, self.ln_f.weight,
+                                  self.ln_f.bias, self.ln_f.eps)
+        cache.lens = cache.lens + n_new
+        return y
+
 
 class GPTNeoForCausalLM(nn.Module):
     config_class = GPTNeoConfig
@@ -298,3 +338,13 @@ class GPTNeoForCausalLM(nn.Module):
         hidden = self.transformer.decode_step(tokens, cache)
         cache.steps += 1
         return arena_linear(self.lm_head, hidden)
+
+    @torch.no_grad()
+    def extend(self, tokens: torch.Tensor, cache,
+               n_new: Optional[torch.Tensor] = None,
+               last_only: bool = False) -> torch.Tensor:
+        """Logits [B, T, V] of T more tokens per sequence, tokens [B, T],
+        given everything already in `cache` (kv_cache.extend has the
+        details: ragged `n_new`, `last_only`); raises ValueError if the T
+        tokens would pass the cache's max_len."""
+        return extend(self, self.transformer, tokens, cache, n_new, last_only)

@@ -1,9 +1,11 @@
 """KV cache for generation: per-layer K / V of every token seen so far, so a
 new token costs one single-token forward (`decode_step`) instead of a
-re-forward of the whole context.
+re-forward of the whole context, and several new tokens one multi-token
+forward (`extend`): chunked prefill, a continued context, scoring a
+continuation.
 
-Layout (ops.kv_append / ops.decode_attention): per layer a `k` and a `v`
-[B, Hkv, max_len, D] in the model's dtype, K stored after RoPE; `lens` int32
+Layout (ops.kv_append / ops.decode_attention / ops.extend_attention): per
+layer a `k` and a `v` [B, Hkv, max_len, D] in the model's dtype, K stored after RoPE; `lens` int32
 [B] on the device = tokens cached per sequence, so a batch may be ragged.
 `lens` is never read on the host: `steps` is the host's own count of the
 longest sequence (the prompt width plus the decode steps taken), which is all
@@ -110,3 +112,60 @@ def prefill(lm, backbone, input_ids: torch.Tensor,
     cache.begin(S, lens)
     last = hidden[torch.arange(B, device=dev), lens.long() - 1]   # [B, hid]
     return arena_linear(lm.lm_head, last)
+
+
+def extend(lm, backbone, tokens: torch.Tensor, cache: KVCache,
+           n_new: Optional[torch.Tensor], last_only: bool) -> torch.Tensor:
+    """Shared body of LlamaForCausalLM.extend / GPTNeoForCausalLM.extend
+    (the callers hold no_grad): T more tokens per sequence, tokens [B, T], on
+    a cache that already holds something. Sequence b takes its first
+    n_new[b] tokens (clamped into [0, T]; None = T); the rest of its row is
+    right-padding: causality keeps it from reaching a valid row, and the cache
+    rows it writes lie beyond the sequence's new length, so they are never
+    read and are overwritten later. Returns logits [B, T, V], or with
+    `last_only` [B, V] at row n_new[b] - 1 (row 0 where n_new[b] == 0), so
+    the head sees one row per sequence."""
+    from acco_amd.models.fuse import arena_linear
+    if tokens.dim() != 2 or tokens.shape[0] != cache.batch \
+            or tokens.shape[1] < 1:
+        raise ValueError(f"tokens must be [B = {cache.batch}, T >= 1], got "
+                         f"{tuple(tokens.shape)}")
+    B, T = tokens.shape
+    cache.room_for(T)
+    dev = tokens.device
+    if n_new is None:
+        n_new = torch.full((B,), T, device=dev, dtype=torch.int32)
+    n_new = n_new.to(device=dev, dtype=torch.int32).clamp(0, T)
+    hidden = backbone.extend(tokens, cache, n_new)
+    cache.steps += T
+    if last_only:
+        row = (n_new.long() - 1).clamp(min=0)
+        hidden = hidden[torch.arange(B, device=dev), row]         # [B, hid]
+    return arena_linear(lm.lm_head, hidden)
+
+
+def prefill_chunked(lm, input_ids: torch.Tensor,
+                    lens: Optional[torch.Tensor], cache: KVCache,
+                    chunk: int) -> torch.Tensor:
+    """`lm.prefill` with activation memory bounded by `chunk` columns:
+    prefill on the first `chunk` columns of the prompt [B, S], then one
+    `extend(..., last_only=True)` per further slice. Returns the logits
+    [B, V] of each sequence's last prompt token, kept per sequence from the
+    slice that holds position lens[b] - 1 by a select on the device (no host
+    read)."""
+    B, S = input_ids.shape
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be >= 1, got {chunk}")
+    dev = input_ids.device
+    if lens is None:
+        lens = torch.full((B,), S, device=dev, dtype=torch.int32)
+    lens = lens.to(device=dev, dtype=torch.int32).clamp(1, S)
+    logits = lm.prefill(input_ids[:, :chunk], lens, cache)
+    for start in range(chunk, S, chunk):
+        width = min(chunk, S - start)
+        n_new = (lens - start).clamp(0, width)
+        nxt = lm.extend(input_ids[:, start:start + width], cache,
+                        n_new=n_new, last_only=True)
+        logits = torch.where((n_new > 0)[:, None], nxt, logits)
+    return logits

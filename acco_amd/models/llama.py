@@ -21,7 +21,7 @@ import torch.nn as nn
 from acco_amd import ops
 from acco_amd.models.config import LlamaConfig
 from acco_amd.models.fuse import arena_linear, arena_lm_loss
-from acco_amd.models.kv_cache import prefill
+from acco_amd.models.kv_cache import extend, prefill
 
 
 class LlamaRMSNorm(nn.Module):
@@ -115,6 +115,21 @@ class LlamaAttention(nn.Module):
         o = ops.decode_attention(q[:, 0], kc, vc, lens1)
         return arena_linear(self.o_proj, o.reshape(B, 1, -1))
 
+    def extend(self, x: torch.Tensor, cache, layer: int) -> torch.Tensor:
+        """T tokens per sequence, x [B, T, hidden]: project, append K (RoPE
+        at position cache.lens[b] + t) and V to layer `layer` of the cache,
+        attend everything cached up to each token's own position."""
+        B, T, _ = x.shape
+        cfg, hd = self.cfg, self.cfg.head_dim
+        q = self.q_proj(x).view(B, T, cfg.num_heads, hd)
+        k = self.k_proj(x).view(B, T, cfg.num_kv_heads, hd)
+        v = self.v_proj(x).view(B, T, cfg.num_kv_heads, hd)
+        cos, sin = cache.rope
+        kc, vc = cache.k[layer], cache.v[layer]
+        q = ops.kv_append(kc, vc, cache.lens, k, v, q, cos, sin)
+        o = ops.extend_attention(q, kc, vc, cache.lens)
+        return arena_linear(self.o_proj, o.reshape(B, T, -1))
+
 
 class LlamaMLP(nn.Module):
     def __init__(self, cfg: LlamaConfig):
@@ -155,15 +170,18 @@ class LlamaDecoderLayer(nn.Module):
         self.post_attention_layernorm = LlamaRMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
     def forward(self, pending, residual, cos, sin, doc_start=None,
-                doc_end=None, kv=None, decode=None):
+                doc_end=None, kv=None, decode=None, extend=None):
         """`kv` (prefill) is handed to the attention; `decode` = (cache,
-        layer index, lens + 1) makes this a single-token step on the cache.
-        Both None: the training forward."""
+        layer index, lens + 1) makes this a single-token step on the cache,
+        `extend` = (cache, layer index) a multi-token one. All None: the
+        training forward."""
         n1 = self.input_layernorm
         h1, residual = ops.add_rms_norm(pending, residual, n1.weight,
                                         n1.variance_epsilon)
         if decode is not None:
             a = self.self_attn.decode(h1, *decode)
+        elif extend is not None:
+            a = self.self_attn.extend(h1, *extend)
         elif kv is not None:
             a = self.self_attn(h1, cos, sin, doc_start, doc_end, kv)
         else:
@@ -256,6 +274,21 @@ class LlamaModel(nn.Module):
         cache.lens = lens1
         return y[:, 0]
 
+    def extend(self, tokens: torch.Tensor, cache,
+               n_new: torch.Tensor) -> torch.Tensor:
+        """Hidden states [B, T, hidden] of T new tokens per sequence at
+        positions cache.lens[b] + t; appends to every layer of the cache and
+        advances cache.lens by n_new (int32 [B]) once, after the last layer."""
+        pending = self.embed_tokens(tokens)
+        residual = None
+        for i, layer in enumerate(self.layers):
+            pending, residual = layer(pending, residual, None, None,
+                                      extend=(cache, i))
+        y, _ = ops.add_rms_norm(pending, residual, self.norm.weight,
+                                self.norm.variance_epsilon)
+        cache.lens = cache.lens + n_new
+        return y
+
 
 class LlamaForCausalLM(nn.Module):
     config_class = LlamaConfig
@@ -327,3 +360,13 @@ class LlamaForCausalLM(nn.Module):
         hidden = self.model.decode_step(tokens, cache)
         cache.steps += 1
         return arena_linear(self.lm_head, hidden)
+
+    @torch.no_grad()
+    def extend(self, tokens: torch.Tensor, cache,
+               n_new: Optional[torch.Tensor] = None,
+               last_only: bool = False) -> torch.Tensor:
+        """Logits [B, T, V] of T more tokens per sequence, tokens [B, T],
+        given everything already in `cache` (kv_cache.extend has the
+        details: ragged `n_new`, `last_only`); raises ValueError if the T
+        tokens would pass the cache's max_len."""
+        return extend(self, self.model, tokens, cache, n_new, last_only)

@@ -275,6 +275,41 @@ def decode_attention_splits(bhkv: int, smax: int) -> Tuple[int, int]:
     return int(n_split), int(chunk)
 
 
+def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, cache_len: torch.Tensor,
+                     scale: Optional[float] = None,
+                     window: Optional[int] = None) -> torch.Tensor:
+    """o [B, T, H, D] of T new query tokens per sequence, q [B, T, H, D],
+    against the caches [B, Hkv, Smax, D] that already hold their K / V:
+    `cache_len` (int32 [B]) is the length before them, the tensor just given
+    to kv_append. Query t sits at p = clamp(cache_len[b], 0, Smax) + t and
+    attends keys [max(0, p + 1 - window), p]; p >= Smax gives +0
+    (torch_ref.extend_attention has the semantics). q may be a strided
+    section of a packed projection. HIP MFMA kernel for bf16, D in {64, 128},
+    1 <= H/Hkv <= 8; the torch reference outside that contract. No host
+    sync."""
+    if (_use_ref(q, "attn_extend") or q.dtype != torch.bfloat16
+            or not _decode_contract(q.shape[2], k_cache)):
+        return torch_ref.extend_attention(q, k_cache, v_cache, cache_len,
+                                          scale=scale, window=window)
+    if scale is None:
+        scale = q.shape[3] ** -0.5
+    return hip_ext().attn_extend(q, k_cache, v_cache, cache_len,
+                                 float(scale), int(window or 0))
+
+
+def extend_attention_splits(bhkv: int, cols: int,
+                            smax: int) -> Tuple[int, int, int]:
+    """(n_blk, n_split, chunk) of the HIP extend attention for B·Hkv
+    (sequence, kv head) pairs, cols = T·H/Hkv query columns per pair and a
+    cache of Smax rows: n_blk blocks of 128 columns, each over n_split
+    workgroups, workgroup i owning keys [i·chunk, (i+1)·chunk). A host
+    function of its three arguments only."""
+    n_blk, n_split, chunk = hip_ext().attn_extend_grid(int(bhkv), int(cols),
+                                                       int(smax))
+    return int(n_blk), int(n_split), int(chunk)
+
+
 def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int, step: int,
                   done: Optional[torch.Tensor] = None, eos_id: int = -1

@@ -1,5 +1,6 @@
-// Shared device code of the four attention files (attention_fwd.hip,
-// attention_fwd32.hip, attention_bwd.hip, attention_bwd32.hip): tile
+// Shared device code of the training attention files (attention_fwd.hip,
+// attention_fwd32.hip, attention_bwd.hip, attention_bwd32.hip) and of the
+// cache kernel attention_extend.hip: tile
 // constants, LDS staging, the 32x32 C-layout helpers, the causal/window tile
 // ranges, every kernel's LDS layout and the host-side choice of kernel
 // generation, and the order in which a grid's workgroups take their (row
@@ -223,6 +224,10 @@ template <int D, int NW> struct FwdLds {         // attn_fwd_kernel
                        bytes = (p + w_tile(NW)) * sizeof(u16);
 };
 template <int D> struct Fwd32Lds {               // attn_fwd32_kernel
+  static constexpr int k_row = 0, v_t = k_row + r_tile(D),
+                       bytes = (v_t + t_tile(D)) * sizeof(u16);
+};
+template <int D> struct ExtendLds {              // attn_extend_kernel
   static constexpr int k_row = 0, v_t = k_row + r_tile(D),
                        bytes = (v_t + t_tile(D)) * sizeof(u16);
 };

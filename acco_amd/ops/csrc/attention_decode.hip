@@ -197,9 +197,9 @@ void attn_decode_kernel(const u16* __restrict__ q,
   }
 }
 
-// o[b, h, :] = sum_i exp2(m_i - M) o_i / sum_i exp2(m_i - M) l_i over the
-// splits i in order; l = 0 (no key at all) stores 0. One block per (b, h),
-// one thread per dim.
+// o[row, :] = sum_i exp2(m_i - M) o_i / sum_i exp2(m_i - M) l_i over the
+// splits i in order; l = 0 (no key at all) stores 0. One block per row of o
+// ((b, h) here, (b, t, h) in attention_extend.hip), one thread per dim.
 __global__ void attn_decode_combine_kernel(const float* __restrict__ part_ml,
                                            const float* __restrict__ part_o,
                                            u16* __restrict__ o, int n_split,
@@ -274,6 +274,14 @@ extern "C" void acco_attn_decode(const void* q, const void* k_cache,
     launch_decode<128>(H / Hkv, grid, stream, (const u16*)q,
                        (const u16*)k_cache, (const u16*)v_cache, cache_len,
                        ml, po, Hkv, Smax, window, chunk, scale_log2, q_rs);
-  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * H), dim3(D), 0,
-                     stream, ml, po, (u16*)o, n_split, D);
+  acco_attn_split_combine(ml, po, o, (long long)B * H, n_split, D, stream);
+}
+
+extern "C" void acco_attn_split_combine(const float* part_ml,
+                                        const float* part_o, void* o,
+                                        long long rows, int n_split, int D,
+                                        hipStream_t stream) {
+  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)rows),
+                     dim3(D), 0, stream, part_ml, part_o, (u16*)o, n_split,
+                     D);
 }

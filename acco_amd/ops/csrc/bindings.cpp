@@ -1149,6 +1149,59 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
   return o;
 }
 
+// T, H / Hkv and the element counts attn_extend's int arithmetic and grid take
+static void check_extend_sizes(int64_t B, int64_t T, int64_t H, int64_t Hkv) {
+  TORCH_CHECK(H > 0 && H % Hkv == 0 && H / Hkv <= 8,
+              "q: need H % Hkv == 0 and 1 <= H/Hkv <= 8, got H=", H, " Hkv=",
+              Hkv);
+  TORCH_CHECK(T >= 1 && T < (1LL << 30) && B * T * H < (1LL << 31) &&
+              T * (H / Hkv) <= 65535LL * 128,
+              "q: need 1 <= T, B*T*H < 2^31 and T*H/Hkv <= 65535*128, got "
+              "B=", B, " T=", T, " H=", H);
+}
+
+// (n_blk, n_split, chunk) of attn_extend for B*Hkv (sequence, kv head) pairs,
+// cols = T * H/Hkv query columns per pair and a cache of Smax rows
+std::vector<int64_t> attn_extend_grid(int64_t BHkv, int64_t cols,
+                                      int64_t Smax) {
+  TORCH_CHECK(BHkv > 0 && cols > 0 && cols < (1LL << 31) && Smax > 0 &&
+              Smax < (1LL << 30), "need BHkv > 0, 0 < cols < 2^31 and "
+              "0 < Smax < 2^30, got BHkv=", BHkv, " cols=", cols, " Smax=",
+              Smax);
+  int n_blk, n_split, chunk;
+  acco_attn_extend_grid((long long)BHkv, (long long)cols, (int)Smax, &n_blk,
+                        &n_split, &chunk);
+  return {n_blk, n_split, chunk};
+}
+
+// o [B, T, H, D] of T query tokens per sequence whose K / V are in the caches
+// already: q [B, T, H, D] bf16 whose token rows may be strided (a section of
+// the packed projection output); cache_len is the length before the T tokens.
+// A window at or beyond Smax bounds nothing and reaches the kernel as 0.
+at::Tensor attn_extend(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
+                       at::Tensor cache_len, double scale, int64_t window) {
+  const auto [B, Hkv, Smax, D] = check_cache_args(k_cache, v_cache, cache_len);
+  TORCH_CHECK(q.dim() == 4, "q must be [B, T, H, D], got ", q.sizes());
+  const int64_t T = q.size(1), H = q.size(2);
+  check_extend_sizes(B, T, H, Hkv);
+  const long long q_rs = check_token_rows(q, k_cache, B, T, H, D, "q");
+  TORCH_CHECK(window >= 0, "window must be >= 0, got ", window);
+  const int win = window >= Smax ? 0 : (int)window;
+  int n_blk, n_split, chunk;
+  acco_attn_extend_grid((long long)B * Hkv, T * (H / Hkv), Smax, &n_blk,
+                        &n_split, &chunk);
+  auto o = at::empty({B, T, H, D}, k_cache.options());
+  auto ws = at::empty(
+      {n_split > 1 ? (int64_t)B * T * H * n_split * (2 + D) : 0},
+      k_cache.options().dtype(at::kFloat));
+  acco_attn_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                   cache_len.data_ptr<int>(), o.data_ptr(),
+                   ws.data_ptr<float>(), B, (int)T, (int)H, Hkv, D, Smax,
+                   (float)scale, win, q_rs, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return o;
+}
+
 // ---- on-device sampling (sample.hip)
 // (token int64 [B], logprob fp32 [B], thr bf16 [B], n_kept int32 [B]) of one
 // draw per row. The argument contract: logits CUDA bf16 [B, V] whose last dim
@@ -1225,6 +1278,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_grid", &attn_decode_grid, py::arg("BHkv"),
         py::arg("Smax"));
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("cache_len"), py::arg("scale"),
+        py::arg("window"));
+  m.def("attn_extend_grid", &attn_extend_grid, py::arg("BHkv"),
+        py::arg("cols"), py::arg("Smax"));
+  m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("cache_len"), py::arg("scale"),
         py::arg("window"));
   m.def("fused_adamw", &fused_adamw,

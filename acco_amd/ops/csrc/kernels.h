@@ -94,6 +94,28 @@ void acco_attn_decode(const void* q, const void* k_cache, const void* v_cache,
                       const int* cache_len, void* o, float* workspace, int B,
                       int H, int Hkv, int D, int Smax, float scale,
                       int window, long long q_rs, hipStream_t stream);
+// The combine of both split kernels: o[row, :] bf16 from the fp32 partials
+// ml [rows, n_split, 2] and o [rows, n_split, D], in split order
+void acco_attn_split_combine(const float* part_ml, const float* part_o,
+                             void* o, long long rows, int n_split, int D,
+                             hipStream_t stream);
+
+// ---- attention_extend.hip
+// T query tokens per sequence against the cache, which already holds their
+// K / V: q [B, T, H, D] (token rows q_rs apart), o [B, T, H, D] contiguous;
+// query t sits at p = clamp(cache_len[b], 0, Smax) + t and attends keys
+// [max(0, p + 1 - window), p], window 0 = none; p >= Smax stores +0.
+// D in {64, 128}, 1 <= H / Hkv <= 8, B * T * H < 2^31. The grid (host only):
+// n_blk blocks of 128 (token, head-in-group) columns per (sequence, kv head),
+// each over n_split workgroups of `chunk` keys, a function of BHkv, cols =
+// T * H / Hkv and Smax. workspace: B * T * H * n_split * (2 + D) fp32 when
+// n_split > 1 (written before it is read), unused otherwise.
+void acco_attn_extend_grid(long long BHkv, long long cols, int Smax,
+                           int* n_blk, int* n_split, int* chunk);
+void acco_attn_extend(const void* q, const void* k_cache, const void* v_cache,
+                      const int* cache_len, void* o, float* workspace, int B,
+                      int T, int H, int Hkv, int D, int Smax, float scale,
+                      int window, long long q_rs, hipStream_t stream);
 
 // ---- ce.hip
 // bf16 logits on a 16-byte aligned base (any V). A token is valid iff

@@ -230,6 +230,51 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return (o / l.clamp(min=torch.finfo(wide).tiny)).to(q.dtype)
 
 
+def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, cache_len: torch.Tensor,
+                     scale: Optional[float] = None,
+                     window: Optional[int] = None) -> torch.Tensor:
+    """Attention of T new query tokens per sequence against the cache, which
+    already holds their K / V (kv_append with the same `cache_len`).
+
+    q [B, T, H, D]; `cache_len` is the length BEFORE the T tokens. With
+    L0 = clamp(cache_len[b], 0, Smax), query t sits at p = L0 + t and attends
+    keys max(0, p + 1 - window) <= j <= p (`window` None or 0 = no window,
+    the convention of decode_attention and causal_attention). A query with
+    p >= Smax (its token was dropped by the append) gives +0. Rows above the
+    keys a query attends are never used, whatever they hold. Math in the
+    wider of q's dtype and fp32; returns [B, T, H, D] in q's dtype. T = 1 is
+    decode_attention(q[:, 0], ..., cache_len + 1)."""
+    B, T, H, D = q.shape
+    Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
+    wide = torch.promote_types(q.dtype, torch.float32)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    L0 = cache_len.long().clamp(0, Smax)
+    p = L0[:, None] + torch.arange(T, device=q.device)[None, :]   # [B, T]
+    j = torch.arange(Smax, device=q.device)
+    allow = (j[None, None, :] <= p[:, :, None]) & (p < Smax)[:, :, None]
+    if window:                                                    # [B, T, Smax]
+        allow = allow & (j[None, None, :] > p[:, :, None] - int(window))
+    # a row no query of the sequence attends is replaced before any arithmetic
+    used = allow.any(1)[:, None, :, None]                         # [B,1,Smax,1]
+    zero = torch.zeros((), dtype=wide, device=q.device)
+    k = torch.where(used, k_cache.to(wide), zero)
+    v = torch.where(used, v_cache.to(wide), zero)
+    if Hkv != H:
+        k = k.repeat_interleave(H // Hkv, dim=1)
+        v = v.repeat_interleave(H // Hkv, dim=1)
+    a4 = allow[:, None]                                           # [B,1,T,Smax]
+    s = torch.einsum("bthd,bhjd->bhtj", q.to(wide), k) * scale
+    s = s.masked_fill(~a4, float("-inf"))
+    m = s.amax(-1, keepdim=True).clamp(min=torch.finfo(wide).min)
+    pr = torch.exp(s - m)                                         # masked: 0
+    l = pr.sum(-1, keepdim=True)
+    o = torch.einsum("bhtj,bhjd->bhtd", pr, v)
+    o = o / l.clamp(min=torch.finfo(wide).tiny)
+    return o.permute(0, 2, 1, 3).to(q.dtype)
+
+
 # ------------------------------------------------- sampling (generation)
 # The executable definition of ops.sample_logits (kernel: csrc/sample.hip).
 # Integer parts (keys, thresholds, the generator) are exact; every real

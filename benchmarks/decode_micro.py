@@ -13,6 +13,11 @@ attention kernel alone.
    to read per second. "hot" calls one cache again and again (at these sizes
    it stays in the L2 / Infinity Cache); "rotating" walks over copies that
    add up to 1 GiB, more than the caches hold.
+3. ops.extend_attention (attn_extend, + combine when the grid splits) at the
+   same heads, (B, T, L0) in {(1, 8, 1024), (8, 8, 4096), (1, 256, 3840)},
+   Smax = L0 + T, by the method of 2, next to what served the same result
+   before it: T successive ops.decode_attention calls (T = 8), or the fp32
+   reference math torch_ref.extend_attention (T = 256).
 
 Prints one JSON line per measurement. Needs a GPU: there is no CPU fallback.
 """
@@ -111,6 +116,52 @@ def bench_decode_kernel(B, L, H=32, Hkv=8, D=64, calls=400,
         "GBps_rotating": cache_bytes / out["rotating"] / 1e9}), flush=True)
 
 
+def bench_extend_kernel(B, T, L0, H=32, Hkv=8, D=64, calls=200,
+                        rotate_bytes=1 << 30):
+    dev, dt = "cuda", torch.bfloat16
+    Smax = L0 + T
+    cache_bytes = 2 * B * Hkv * Smax * D * 2         # K and V, bf16
+    copies = max(1, min(512, -(-rotate_bytes // cache_bytes)))
+    kcs = [torch.randn(B, Hkv, Smax, D, device=dev, dtype=dt)
+           for _ in range(copies)]
+    vcs = [torch.randn(B, Hkv, Smax, D, device=dev, dtype=dt)
+           for _ in range(copies)]
+    q = torch.randn(B, T, H, D, device=dev, dtype=dt)
+    lens = torch.full((B,), L0, device=dev, dtype=torch.int32)
+    lens_t = [lens + t + 1 for t in range(T)]
+    n_blk, n_split, chunk = ops.extend_attention_splits(
+        B * Hkv, T * (H // Hkv), Smax)
+
+    def extend(kc, vc):
+        ops.extend_attention(q, kc, vc, lens)
+
+    def decodes(kc, vc):
+        for t in range(T):
+            ops.decode_attention(q[:, t], kc, vc, lens_t[t])
+
+    def reference(kc, vc):
+        ops.torch_ref.extend_attention(q, kc, vc, lens)
+
+    base_name, base = (("decode_x_T", decodes) if T <= 8
+                       else ("fp32_reference", reference))
+    out = {}
+    for name, fn, count in (("extend", extend, calls),
+                            (base_name, base, max(10, calls // T))):
+        for mode, n in (("hot", 1), ("rotating", copies)):
+            def loop(k):
+                for i in range(k):
+                    fn(kcs[i % n], vcs[i % n])
+            loop(max(5, min(n, count)))              # warm-up
+            torch.cuda.synchronize()
+            sec, _ = event_seconds(lambda: loop(count))
+            out[name + "_" + mode] = sec / count * 1e6
+    print(json.dumps({
+        "bench": "attn_extend", "B": B, "T": T, "L0": L0, "H": H, "Hkv": Hkv,
+        "D": D, "n_blk": n_blk, "n_split": n_split, "chunk": chunk,
+        "cache_bytes": cache_bytes, "copies": copies, "baseline": base_name,
+        **{"us_" + k: v for k, v in out.items()}}), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama-1b")
@@ -131,6 +182,8 @@ def main(argv=None):
         for B in (1, 8):
             for L in (1024, 4096):
                 bench_decode_kernel(B, L)
+        for B, T, L0 in ((1, 8, 1024), (8, 8, 4096), (1, 256, 3840)):
+            bench_extend_kernel(B, T, L0)
 
 
 if __name__ == "__main__":

@@ -9,7 +9,8 @@ code and the seeded generator, which run on the CPU: the logits are copied to
 the host every token. --device-sampling (implies --kv-cache) runs
 acco_amd.models.generate instead: top-k / top-p and the draw happen on the
 model's device from a counter-based generator, so the same --seed gives other
-tokens than the CPU paths. Beyond the reference's surface (it has no
+tokens than the CPU paths. --prefill-chunk N (implies --kv-cache) pushes the
+prompt through the cache N tokens at a time. Beyond the reference's surface (it has no
 generation path); useful for judging what a checkpoint learned.
 
 Usage (config overrides use the same syntax as main.py):
@@ -42,12 +43,13 @@ def _sample(step: torch.Tensor, temperature: float,
 @torch.no_grad()
 def generate(model, ids: torch.Tensor, max_new: int, temperature: float,
              max_len: int, seed: int = 0,
-             use_cache: bool = False) -> torch.Tensor:
+             use_cache: bool = False,
+             prefill_chunk: int = 0) -> torch.Tensor:
     gen = torch.Generator(device="cpu").manual_seed(seed)
     model.eval()
-    if use_cache:
+    if use_cache or prefill_chunk > 0:
         return _generate_cached(model, ids, max_new, temperature, max_len,
-                                gen)
+                                gen, prefill_chunk)
     for _ in range(max_new):
         out = model(ids[:, -max_len:])
         logits = out[0] if isinstance(out, tuple) else out
@@ -56,10 +58,12 @@ def generate(model, ids: torch.Tensor, max_new: int, temperature: float,
     return ids
 
 
-def _generate_cached(model, ids, max_new, temperature, max_len, gen):
-    """One prefill, then one decode_step per token; there is no sliding
-    window over the context here, so it all has to fit."""
-    from acco_amd.models.kv_cache import KVCache
+def _generate_cached(model, ids, max_new, temperature, max_len, gen,
+                     prefill_chunk=0):
+    """One prefill (in slices of `prefill_chunk` tokens when that is set),
+    then one decode_step per token; there is no sliding window over the
+    context here, so it all has to fit."""
+    from acco_amd.models.kv_cache import KVCache, prefill_chunked
     total = ids.shape[1] + max_new
     if total > max_len:
         raise ValueError(
@@ -69,7 +73,10 @@ def _generate_cached(model, ids, max_new, temperature, max_len, gen):
     if max_new <= 0:
         return ids
     cache = KVCache.allocate(model, ids.shape[0], total)
-    logits = model.prefill(ids, None, cache)
+    if 0 < prefill_chunk < ids.shape[1]:
+        logits = prefill_chunked(model, ids, None, cache, prefill_chunk)
+    else:
+        logits = model.prefill(ids, None, cache)
     for i in range(max_new):
         nxt = _sample(logits.float().cpu(), temperature, gen).to(ids.device)
         ids = torch.cat([ids, nxt], dim=1)
@@ -92,6 +99,10 @@ def main(argv=None) -> str:
                     help="prefill once, then one cached decode step per "
                          "token (needs prompt + max-new <= "
                          "max_position_embeddings)")
+    ap.add_argument("--prefill-chunk", type=int, default=0,
+                    help="push the prompt through the cache this many "
+                         "tokens at a time (implies --kv-cache; 0 = one "
+                         "prefill of the whole prompt)")
     ap.add_argument("--device-sampling", action="store_true",
                     help="sample on the model's device with "
                          "acco_amd.models.generate (implies --kv-cache): no "
@@ -105,6 +116,8 @@ def main(argv=None) -> str:
     ap.add_argument("overrides", nargs="*",
                     help="config overrides, e.g. model=gptneo")
     args = ap.parse_args(argv)
+    if args.prefill_chunk < 0:
+        ap.error("need --prefill-chunk >= 0")
     if args.top_k < 0 or not args.top_p > 0:
         ap.error("need --top-k >= 0 and --top-p > 0")
     if (args.top_k != 0 or args.top_p < 1.0) and not args.device_sampling:
@@ -132,11 +145,13 @@ def main(argv=None) -> str:
         out, n_new = generate_on_device(
             model, ids, max_new=max(args.max_new, 0),
             temperature=max(args.temperature, 0.0), top_k=args.top_k,
-            top_p=args.top_p, seed=args.seed)
+            top_p=args.top_p, seed=args.seed,
+            prefill_chunk=args.prefill_chunk)
         out = out[:, :ids.shape[1] + int(n_new[0])]
     else:
         out = generate(model, ids, args.max_new, args.temperature, max_len,
-                       seed=args.seed, use_cache=args.kv_cache)
+                       seed=args.seed, use_cache=args.kv_cache,
+                       prefill_chunk=args.prefill_chunk)
     text = tok.decode(out[0].tolist())
     print(text)
     return text
