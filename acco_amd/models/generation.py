@@ -21,7 +21,9 @@ def generate(model, input_ids: torch.Tensor,
              lens: Optional[torch.Tensor] = None, *, max_new: int,
              temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
              seed: int = 0, eos_token_id: Optional[int] = None,
-             prefill_chunk: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+             prefill_chunk: int = 0,
+             kv_dtype: Optional[torch.dtype] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
     """(tokens int64 [B, S + max_new], n_generated int64 [B]) for prompts
     `input_ids` [B, S] of `model` (LlamaForCausalLM or GPTNeoForCausalLM, in
     eval mode). Sequence b holds lens[b] <= S prompt tokens (None = all S),
@@ -36,7 +38,10 @@ def generate(model, input_ids: torch.Tensor,
     n_generated[b] counts b's tokens up to and including its first eos.
     prefill_chunk (0 < prefill_chunk < S): the prompt goes through the cache
     in slices of that many columns (kv_cache.prefill_chunked), which bounds
-    the prefill's activation memory; 0 = one prefill of the whole prompt."""
+    the prefill's activation memory; 0 = one prefill of the whole prompt.
+    kv_dtype: the dtype of the KV cache (KVCache.allocate; None = the
+    model's); torch.float8_e4m3fn stores it quantised, about half the bytes
+    per cached token."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B, S], got {input_ids.shape}")
     B, S = input_ids.shape
@@ -70,7 +75,7 @@ def generate(model, input_ids: torch.Tensor,
     done = None
     if eos_token_id is not None:
         done = torch.zeros(B, device=dev, dtype=torch.uint8)
-    cache = KVCache.allocate(model, B, total)
+    cache = KVCache.allocate(model, B, total, dtype=kv_dtype)
     if 0 < int(prefill_chunk) < S:
         logits = prefill_chunked(model, input_ids, lens, cache, prefill_chunk)
     else:

@@ -41,9 +41,10 @@ class GPTNeoSelfAttention(nn.Module):
                 doc_start: Optional[torch.Tensor] = None,
                 doc_end: Optional[torch.Tensor] = None,
                 kv=None) -> torch.Tensor:
-        """`kv` = (k_cache, v_cache, cache_len), prefill only: K and V of
-        every position are also appended to the cache; None (the training
-        forward) launches nothing for it."""
+        """`kv` = (k_cache, v_cache, cache_len, scales), prefill only: K and
+        V of every position are also appended to the cache (`scales` =
+        KVCache.scales(layer)); None (the training forward) launches nothing
+        for it."""
         B, S, d = x.shape
         H, hd = self.cfg.num_heads, self.cfg.head_dim
         if self._fused_kvq is not None:
@@ -65,7 +66,7 @@ class GPTNeoSelfAttention(nn.Module):
                     _ops.kv_append(
                         kv[0], kv[1], kv[2],
                         kvq[..., :d].unflatten(-1, (H, hd)),
-                        kvq[..., d:2 * d].unflatten(-1, (H, hd)))
+                        kvq[..., d:2 * d].unflatten(-1, (H, hd)), **kv[3])
                 return arena_linear(self.out_proj, o)
             k, v, q = torch.split(kvq, splits, dim=-1)
             q = q.contiguous().view(B, S, H, hd)
@@ -77,7 +78,7 @@ class GPTNeoSelfAttention(nn.Module):
             v = self.v_proj(x).view(B, S, H, hd)
         window = self.cfg.window_size if self.attention_type == "local" else None
         if kv is not None:
-            ops.kv_append(kv[0], kv[1], kv[2], k, v)
+            ops.kv_append(kv[0], kv[1], kv[2], k, v, **kv[3])
         if doc_start is None:
             o = ops.causal_attention(q, k, v, scale=1.0, window=window)
         else:
@@ -97,11 +98,12 @@ class GPTNeoSelfAttention(nn.Module):
         q = self.q_proj(x).view(B, H, hd)
         k = self.k_proj(x).view(B, 1, H, hd)
         v = self.v_proj(x).view(B, 1, H, hd)
-        kc, vc = cache.k[layer], cache.v[layer]
-        ops.kv_append(kc, vc, cache.lens, k, v)
+        kc, vc, sc = cache.k[layer], cache.v[layer], cache.scales(layer)
+        ops.kv_append(kc, vc, cache.lens, k, v, **sc)
         window = (self.cfg.window_size
                   if self.attention_type == "local" else None)
-        o = ops.decode_attention(q, kc, vc, lens1, scale=1.0, window=window)
+        o = ops.decode_attention(q, kc, vc, lens1, scale=1.0, window=window,
+                                 **sc)
         return arena_linear(self.out_proj, o.reshape(B, 1, -1))
 
     def extend(self, x: torch.Tensor, cache, layer: int) -> torch.Tensor:
@@ -114,12 +116,12 @@ class GPTNeoSelfAttention(nn.Module):
         q = self.q_proj(x).view(B, T, H, hd)
         k = self.k_proj(x).view(B, T, H, hd)
         v = self.v_proj(x).view(B, T, H, hd)
-        kc, vc = cache.k[layer], cache.v[layer]
-        ops.kv_append(kc, vc, cache.lens, k, v)
+        kc, vc, sc = cache.k[layer], cache.v[layer], cache.scales(layer)
+        ops.kv_append(kc, vc, cache.lens, k, v, **sc)
         window = (self.cfg.window_size
                   if self.attention_type == "local" else None)
         o = ops.extend_attention(q, kc, vc, cache.lens, scale=1.0,
-                                 window=window)
+                                 window=window, **sc)
         return arena_linear(self.out_proj, o.reshape(B, T, -1))
 
 
@@ -202,7 +204,7 @@ class GPTNeoModel(nn.Module):
             for i, block in enumerate(self.h):
                 pending, residual = block(
                     pending, residual,
-                    kv=(cache.k[i], cache.v[i], cache.lens))
+                    kv=(cache.k[i], cache.v[i], cache.lens, cache.scales(i)))
             y, _ = ops.add_layer_norm(pending, residual, self.ln_f.weight,
                                       self.ln_f.bias, self.ln_f.eps)
             return y

@@ -7,6 +7,12 @@ continuation.
 Layout (ops.kv_append / ops.decode_attention / ops.extend_attention): per
 layer a `k` and a `v` [B, Hkv, max_len, D] in the model's dtype, K stored after RoPE; `lens` int32
 [B] on the device = tokens cached per sequence, so a batch may be ragged.
+With dtype torch.float8_e4m3fn the caches hold OCP e4m3 codes and per layer a
+`k_scale` and a `v_scale` [B, Hkv, max_len] fp32 hold one scale per cache row
+(a row's value is code * scale, torch_ref.kv_quantize): D + 4 bytes per row
+instead of 2 D. The scale is computed by the append itself, from the bf16 row
+it would have stored: no calibration pass and no host sync. Prefill still
+attends the bf16 K / V in flight; decode_step and extend read the codes.
 `lens` is never read on the host: `steps` is the host's own count of the
 longest sequence (the prompt width plus the decode steps taken), which is all
 that is needed to refuse a step past `max_len`."""
@@ -21,8 +27,12 @@ import torch
 class KVCache:
     def __init__(self, k: List[torch.Tensor], v: List[torch.Tensor],
                  lens: torch.Tensor, max_len: int,
-                 rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                 rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                 k_scale: Optional[List[torch.Tensor]] = None,
+                 v_scale: Optional[List[torch.Tensor]] = None):
         self.k, self.v = k, v
+        # per-layer row scales of an e4m3 cache, None for any other dtype
+        self.k_scale, self.v_scale = k_scale, v_scale
         self.lens = lens
         self.max_len = int(max_len)
         self.rope = rope      # fp32 (cos, sin) [max_len, D], Llama only
@@ -33,7 +43,8 @@ class KVCache:
                  dtype=None) -> "KVCache":
         """An empty cache for `batch` sequences of up to `max_len` tokens of
         `model` (LlamaForCausalLM or GPTNeoForCausalLM). `device` / `dtype`
-        default to those of the model's parameters."""
+        default to those of the model's parameters; dtype
+        torch.float8_e4m3fn gives the quantised cache with its scales."""
         cfg = model.cfg
         if not 1 <= int(max_len) <= int(cfg.max_position_embeddings):
             raise ValueError(
@@ -47,6 +58,11 @@ class KVCache:
         n = int(cfg.num_layers)
         k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(n)]
         v = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(n)]
+        k_scale = v_scale = None
+        if dtype == torch.float8_e4m3fn:
+            k_scale, v_scale = (
+                [torch.zeros(shape[:3], device=device, dtype=torch.float32)
+                 for _ in range(n)] for _ in range(2))
         lens = torch.zeros(int(batch), device=device, dtype=torch.int32)
         rope = None
         if hasattr(cfg, "rope_theta"):
@@ -54,7 +70,14 @@ class KVCache:
             # row p of these equals row p of the table of any full forward
             rope = torch_ref.rope_cos_sin(int(max_len), int(cfg.head_dim),
                                           cfg.rope_theta, device)
-        return cls(k, v, lens, max_len, rope)
+        return cls(k, v, lens, max_len, rope, k_scale, v_scale)
+
+    def scales(self, layer: int) -> dict:
+        """The k_scale / v_scale keyword arguments of the cache ops for
+        `layer`: its row scales, or None twice without an e4m3 cache."""
+        if self.k_scale is None:
+            return dict(k_scale=None, v_scale=None)
+        return dict(k_scale=self.k_scale[layer], v_scale=self.v_scale[layer])
 
     @property
     def batch(self) -> int:

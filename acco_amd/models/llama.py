@@ -49,9 +49,10 @@ class LlamaAttention(nn.Module):
                 doc_start: Optional[torch.Tensor] = None,
                 doc_end: Optional[torch.Tensor] = None,
                 kv=None) -> torch.Tensor:
-        """`kv` = (k_cache, v_cache, cache_len), prefill only: the post-RoPE
-        K and V of every position are also appended to the cache; None (the
-        training forward) launches nothing for it."""
+        """`kv` = (k_cache, v_cache, cache_len, scales), prefill only: the
+        post-RoPE K and V of every position are also appended to the cache
+        (`scales` = KVCache.scales(layer)); None (the training forward)
+        launches nothing for it."""
         B, S, _ = x.shape
         cfg = self.cfg
         # keep everything in the projections' natural [B, S, H, D] layout:
@@ -78,7 +79,8 @@ class LlamaAttention(nn.Module):
                     ops.kv_append(
                         kv[0], kv[1], kv[2],
                         roped[..., offs[1]:offs[1] + kw].unflatten(-1, (-1, hd)),
-                        roped[..., offs[2]:offs[2] + kw].unflatten(-1, (-1, hd)))
+                        roped[..., offs[2]:offs[2] + kw].unflatten(-1, (-1, hd)),
+                        **kv[3])
                 return arena_linear(self.o_proj, o)
             q, k, v = torch.split(qkv, splits, dim=-1)
             q = q.contiguous().view(B, S, cfg.num_heads, cfg.head_dim)
@@ -90,7 +92,7 @@ class LlamaAttention(nn.Module):
             v = self.v_proj(x).view(B, S, cfg.num_kv_heads, cfg.head_dim)
         q, k = ops.rope_apply(q, k, cos, sin)
         if kv is not None:
-            ops.kv_append(kv[0], kv[1], kv[2], k, v)
+            ops.kv_append(kv[0], kv[1], kv[2], k, v, **kv[3])
         if doc_start is None:
             o = ops.causal_attention(q, k, v)      # [B, S, H, D]
         else:
@@ -110,9 +112,9 @@ class LlamaAttention(nn.Module):
         k = self.k_proj(x).view(B, 1, cfg.num_kv_heads, hd)
         v = self.v_proj(x).view(B, 1, cfg.num_kv_heads, hd)
         cos, sin = cache.rope
-        kc, vc = cache.k[layer], cache.v[layer]
-        q = ops.kv_append(kc, vc, cache.lens, k, v, q, cos, sin)
-        o = ops.decode_attention(q[:, 0], kc, vc, lens1)
+        kc, vc, sc = cache.k[layer], cache.v[layer], cache.scales(layer)
+        q = ops.kv_append(kc, vc, cache.lens, k, v, q, cos, sin, **sc)
+        o = ops.decode_attention(q[:, 0], kc, vc, lens1, **sc)
         return arena_linear(self.o_proj, o.reshape(B, 1, -1))
 
     def extend(self, x: torch.Tensor, cache, layer: int) -> torch.Tensor:
@@ -125,9 +127,9 @@ class LlamaAttention(nn.Module):
         k = self.k_proj(x).view(B, T, cfg.num_kv_heads, hd)
         v = self.v_proj(x).view(B, T, cfg.num_kv_heads, hd)
         cos, sin = cache.rope
-        kc, vc = cache.k[layer], cache.v[layer]
-        q = ops.kv_append(kc, vc, cache.lens, k, v, q, cos, sin)
-        o = ops.extend_attention(q, kc, vc, cache.lens)
+        kc, vc, sc = cache.k[layer], cache.v[layer], cache.scales(layer)
+        q = ops.kv_append(kc, vc, cache.lens, k, v, q, cos, sin, **sc)
+        o = ops.extend_attention(q, kc, vc, cache.lens, **sc)
         return arena_linear(self.o_proj, o.reshape(B, T, -1))
 
 
@@ -229,7 +231,7 @@ class LlamaModel(nn.Module):
             for i, layer in enumerate(self.layers):
                 pending, residual = layer(
                     pending, residual, cos, sin,
-                    kv=(cache.k[i], cache.v[i], cache.lens))
+                    kv=(cache.k[i], cache.v[i], cache.lens, cache.scales(i)))
             y, _ = ops.add_rms_norm(pending, residual, self.norm.weight,
                                     self.norm.variance_epsilon)
             return y

@@ -216,18 +216,43 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 # ------------------------------------------------ KV cache (generation)
 
-def _decode_contract(q_heads: int, k_cache: torch.Tensor) -> bool:
-    """What the cache kernels take: bf16, D in {64, 128}, 1 <= H/Hkv <= 8."""
+def _decode_contract(q_heads: int, k_cache: torch.Tensor,
+                     dtype: torch.dtype = torch.bfloat16) -> bool:
+    """What the cache kernels take: a bf16 cache (e4m3 for the _fp8 entry
+    points), D in {64, 128}, 1 <= H/Hkv <= 8."""
     Hkv, D = k_cache.shape[1], k_cache.shape[3]
-    return (k_cache.dtype == torch.bfloat16 and D in (64, 128)
+    return (k_cache.dtype == dtype and D in (64, 128)
             and q_heads % Hkv == 0 and 1 <= q_heads // Hkv <= 8)
+
+
+FP8 = torch.float8_e4m3fn
+
+
+def _fp8_cache(k_cache: torch.Tensor, v_cache: torch.Tensor,
+               k_scale: Optional[torch.Tensor],
+               v_scale: Optional[torch.Tensor]) -> bool:
+    """True for an e4m3 cache with both row scales, False for any other
+    cache without scales; a mismatched pair is an error."""
+    fp8 = k_cache.dtype == FP8 or v_cache.dtype == FP8
+    if fp8 != (k_scale is not None) or fp8 != (v_scale is not None) \
+            or k_cache.dtype != v_cache.dtype:
+        raise ValueError(
+            "a float8_e4m3fn KV cache needs k_scale and v_scale [B, Hkv, "
+            "Smax] fp32, and any other cache takes none: got caches "
+            f"{k_cache.dtype} / {v_cache.dtype}, k_scale "
+            f"{'given' if k_scale is not None else 'None'}, v_scale "
+            f"{'given' if v_scale is not None else 'None'}")
+    return fp8
 
 
 def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
               cache_len: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               q: Optional[torch.Tensor] = None,
               cos: Optional[torch.Tensor] = None,
-              sin: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+              sin: Optional[torch.Tensor] = None, *,
+              k_scale: Optional[torch.Tensor] = None,
+              v_scale: Optional[torch.Tensor] = None
+              ) -> Optional[torch.Tensor]:
     """Append k, v [B, T, Hkv, D] to the caches [B, Hkv, Smax, D] at row
     cache_len[b] + t, in place; rows at or beyond Smax are dropped and
     `cache_len` (int32 [B], on the device) is left alone (torch_ref.kv_append
@@ -237,8 +262,20 @@ def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
     k, v and q may be views of the packed projection output (a column
     section `[..., off:off + h*D]` viewed as [B, T, h, D]): the HIP kernel
     reads them through their row stride, no copies. One launch, no host
-    sync."""
+    sync.
+
+    A float8_e4m3fn cache comes with `k_scale` / `v_scale` (fp32 [B, Hkv,
+    Smax], one scale per cache row): each appended row is quantised from its
+    bf16 bits (torch_ref.kv_quantize has the format), in the same launch."""
     heads = q.shape[2] if q is not None else k_cache.shape[1]
+    if _fp8_cache(k_cache, v_cache, k_scale, v_scale):
+        if (_use_ref(k_cache, "kv_append_fp8") or k.dtype != torch.bfloat16
+                or not _decode_contract(heads, k_cache, FP8)):
+            return torch_ref.kv_append(k_cache, v_cache, cache_len, k, v, q,
+                                       cos, sin, k_scale, v_scale)
+        return hip_ext().kv_append_fp8(q if cos is not None else None, k, v,
+                                       cos, sin, k_cache, v_cache, k_scale,
+                                       v_scale, cache_len)
     if (_use_ref(k_cache, "kv_append") or k.dtype != torch.bfloat16
             or not _decode_contract(heads, k_cache)):
         return torch_ref.kv_append(k_cache, v_cache, cache_len, k, v, q,
@@ -250,13 +287,28 @@ def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, cache_len: torch.Tensor,
                      scale: Optional[float] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
+                     window: Optional[int] = None, *,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """o [B, H, D] of one query token per sequence, q [B, H, D], against the
     caches [B, Hkv, Smax, D]: the query is the last of cache_len[b] cached
     tokens and attends keys [max(0, L - window), L), L = clamp(cache_len[b],
     0, Smax) (torch_ref.decode_attention has the semantics). HIP
     flash-decoding kernel for bf16, D in {64, 128}, 1 <= H/Hkv <= 8; the
-    torch reference outside that contract. No host sync."""
+    torch reference outside that contract. No host sync. A float8_e4m3fn
+    cache comes with its row scales `k_scale` / `v_scale` (kv_append) and
+    takes the fp8 variant of the kernel, under the same contract."""
+    if _fp8_cache(k_cache, v_cache, k_scale, v_scale):
+        if (_use_ref(q, "attn_decode_fp8") or q.dtype != torch.bfloat16
+                or not _decode_contract(q.shape[1], k_cache, FP8)):
+            return torch_ref.decode_attention(
+                q, k_cache, v_cache, cache_len, scale=scale, window=window,
+                k_scale=k_scale, v_scale=v_scale)
+        if scale is None:
+            scale = q.shape[2] ** -0.5
+        return hip_ext().attn_decode_fp8(q, k_cache, v_cache, k_scale,
+                                         v_scale, cache_len, float(scale),
+                                         int(window or 0))
     if (_use_ref(q, "attn_decode") or q.dtype != torch.bfloat16
             or not _decode_contract(q.shape[1], k_cache)):
         return torch_ref.decode_attention(q, k_cache, v_cache, cache_len,
@@ -278,7 +330,9 @@ def decode_attention_splits(bhkv: int, smax: int) -> Tuple[int, int]:
 def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, cache_len: torch.Tensor,
                      scale: Optional[float] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
+                     window: Optional[int] = None, *,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """o [B, T, H, D] of T new query tokens per sequence, q [B, T, H, D],
     against the caches [B, Hkv, Smax, D] that already hold their K / V:
     `cache_len` (int32 [B]) is the length before them, the tensor just given
@@ -287,7 +341,19 @@ def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
     (torch_ref.extend_attention has the semantics). q may be a strided
     section of a packed projection. HIP MFMA kernel for bf16, D in {64, 128},
     1 <= H/Hkv <= 8; the torch reference outside that contract. No host
-    sync."""
+    sync. A float8_e4m3fn cache comes with its row scales `k_scale` /
+    `v_scale`, as in decode_attention."""
+    if _fp8_cache(k_cache, v_cache, k_scale, v_scale):
+        if (_use_ref(q, "attn_extend_fp8") or q.dtype != torch.bfloat16
+                or not _decode_contract(q.shape[2], k_cache, FP8)):
+            return torch_ref.extend_attention(
+                q, k_cache, v_cache, cache_len, scale=scale, window=window,
+                k_scale=k_scale, v_scale=v_scale)
+        if scale is None:
+            scale = q.shape[3] ** -0.5
+        return hip_ext().attn_extend_fp8(q, k_cache, v_cache, k_scale,
+                                         v_scale, cache_len, float(scale),
+                                         int(window or 0))
     if (_use_ref(q, "attn_extend") or q.dtype != torch.bfloat16
             or not _decode_contract(q.shape[2], k_cache)):
         return torch_ref.extend_attention(q, k_cache, v_cache, cache_len,

@@ -229,7 +229,11 @@ template <int D> struct Fwd32Lds {               // attn_fwd32_kernel
 };
 template <int D> struct ExtendLds {              // attn_extend_kernel
   static constexpr int k_row = 0, v_t = k_row + r_tile(D),
-                       bytes = (v_t + t_tile(D)) * sizeof(u16);
+                       bytes = (v_t + t_tile(D)) * sizeof(u16),
+                       scales = v_t + t_tile(D),   // e4m3 cache: float
+                                                   // [2][TILE], K then V
+                       bytes_fp8 = bytes + 2 * TILE * sizeof(float);
+  static_assert(bytes % 16 == 0, "scale rows are read as float4");
 };
 template <int D, int NW> struct BwdDqLds {       // attn_bwd_dq_kernel
   static constexpr int k_t = 0, k_row = k_t + t_tile(D),

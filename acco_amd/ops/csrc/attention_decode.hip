@@ -27,12 +27,18 @@
 // wave or split merges as weight exp2(kNegBig - m) = 0 (or 1 against another
 // empty one, times l = 0) and never as exp2(-inf - (-inf)). L = 0 gives o = 0.
 //
+// attn_decode_fp8_kernel is the same skeleton for an e4m3 cache (one-byte
+// codes and one fp32 scale per row): half the K / V bytes per key, so the
+// lanes regroup (its own comment below); both kernels end in decode_finish.
+//
 // The split count is a guess that nobody has measured: about two workgroups
 // per CU (512) over B * Hkv, at least 256 keys per split, at most 64 splits.
 // Sizes tried so far: Smax 256 .. 4096 with B * Hkv 1 .. 64 (the tests and
 // benchmarks/decode_micro.py), for correctness and one timing run only.
 
 #include "common.h"
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace {
@@ -52,6 +58,80 @@ ACCO_DEV void unpack8(const uint4& raw, float* f) {
   for (int i = 0; i < 8; ++i) f[i] = bf16_to_f32(p[i]);
 }
 
+// The end of both decode kernels: a lane holds (m, l, o[E dims]) per head for
+// the keys its lane group took, G = D / E lanes per group, dims c0 .. c0 + E.
+// Merges the groups of a wave, then the four waves through LDS, and stores
+// the block's partial in wave order.
+template <int D, int REP, int E>
+ACCO_DEV void decode_finish(float (&m)[REP], float (&l)[REP],
+                            float (&o)[REP][E], int c0, int bk, int split,
+                            int n_split, float* __restrict__ part_ml,
+                            float* __restrict__ part_o) {
+  constexpr int G = D / E;
+  constexpr int NG = kThreads / G;
+  constexpr int GPW = kWave / G;
+  const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+  // merge the lane groups of a wave (same dims, other keys): xor over the
+  // group index bits, every lane ends with the wave's (m, l, o)
+#pragma unroll
+  for (int h = 0; h < REP; ++h) {
+    float mw = m[h];
+#pragma unroll
+    for (int off = G; off < kWave; off <<= 1)
+      mw = fmaxf(mw, __shfl_xor(mw, off));
+    const float w = exp2_fast(m[h] - mw);
+    float lw = l[h] * w;
+#pragma unroll
+    for (int off = G; off < kWave; off <<= 1) lw += __shfl_xor(lw, off);
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+      float x = o[h][i] * w;
+#pragma unroll
+      for (int off = G; off < kWave; off <<= 1) x += __shfl_xor(x, off);
+      o[h][i] = x;
+    }
+    m[h] = mw;
+    l[h] = lw;
+  }
+  static_assert(GPW >= 1 && NG % GPW == 0, "whole lane groups per wave");
+
+  // the four waves meet in LDS; the block's partial goes out in wave order
+  __shared__ float s_m[kWaves][REP], s_l[kWaves][REP];
+  __shared__ float s_o[kWaves][REP][D];
+  if (lane < G) {
+#pragma unroll
+    for (int h = 0; h < REP; ++h) {
+      if (lane == 0) {
+        s_m[wave][h] = m[h];
+        s_l[wave][h] = l[h];
+      }
+#pragma unroll
+      for (int i = 0; i < E; ++i) s_o[wave][h][c0 + i] = o[h][i];
+    }
+  }
+  __syncthreads();
+  const long long head0 = (long long)bk * REP;    // b * H + kvh * REP
+  for (int t = tid; t < REP * D; t += kThreads) {
+    const int h = t / D, d = t % D;
+    float mb = s_m[0][h];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) mb = fmaxf(mb, s_m[w][h]);
+    float lb = 0.f, ob = 0.f;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      const float wt = exp2_fast(s_m[w][h] - mb);
+      lb = __fmaf_rn(s_l[w][h], wt, lb);
+      ob = __fmaf_rn(s_o[w][h][d], wt, ob);
+    }
+    const long long slot = (head0 + h) * n_split + split;
+    part_o[slot * D + d] = ob;
+    if (d == 0) {
+      part_ml[slot * 2] = mb;
+      part_ml[slot * 2 + 1] = lb;
+    }
+  }
+}
+
 // workspace layout, fp32: ml [B*H, n_split, 2] then o [B*H, n_split, D]
 template <int D, int REP>
 __global__ __launch_bounds__(kThreads)
@@ -65,11 +145,10 @@ void attn_decode_kernel(const u16* __restrict__ q,
                         long long q_rs) {
   constexpr int G = D / 8;            // lanes per key row
   constexpr int NG = kThreads / G;    // key rows per block step
-  constexpr int GPW = kWave / G;      // lane groups per wave
   const int split = blockIdx.x, n_split = gridDim.x;
   const int bk = blockIdx.y;          // b * Hkv + kv head
   const int b = bk / Hkv, kvh = bk % Hkv;
-  const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
+  const int tid = threadIdx.x;
   const int g = tid / G, c8 = (tid % G) * 8;
 
   const int L = min(max(cache_len[b], 0), Smax);
@@ -136,66 +215,144 @@ void attn_decode_kernel(const u16* __restrict__ q,
     step(k0, v0);
   }
 
-  // merge the lane groups of a wave (same dims, other keys): xor over the
-  // group index bits, every lane ends with the wave's (m, l, o)
-#pragma unroll
-  for (int h = 0; h < REP; ++h) {
-    float mw = m[h];
-#pragma unroll
-    for (int off = G; off < kWave; off <<= 1)
-      mw = fmaxf(mw, __shfl_xor(mw, off));
-    const float w = exp2_fast(m[h] - mw);
-    float lw = l[h] * w;
-#pragma unroll
-    for (int off = G; off < kWave; off <<= 1) lw += __shfl_xor(lw, off);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float x = o[h][i] * w;
-#pragma unroll
-      for (int off = G; off < kWave; off <<= 1) x += __shfl_xor(x, off);
-      o[h][i] = x;
-    }
-    m[h] = mw;
-    l[h] = lw;
-  }
-  static_assert(GPW >= 1 && NG % GPW == 0, "whole lane groups per wave");
+  decode_finish<D, REP, 8>(m, l, o, c8, bk, split, n_split, part_ml, part_o);
+}
 
-  // the four waves meet in LDS; the block's partial goes out in wave order
-  __shared__ float s_m[kWaves][REP], s_l[kWaves][REP];
-  __shared__ float s_o[kWaves][REP][D];
-  if (lane < G) {
+// This kernel's device code is built without the packed fp32 VALU ops (see
+// attention_extend.hip); the kernel above keeps the build it was measured
+// with. The host pass does not know the feature, hence the guard.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                      \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+
+// E e4m3 codes (E / 4 dwords) -> fp32 by v_cvt_pk_f32_fp8, two values per
+// instruction
+template <int E, class Raw>
+ACCO_DEV void unpack_fp8(const Raw& raw, float* f) {
+  const int* w = reinterpret_cast<const int*>(&raw);
 #pragma unroll
-    for (int h = 0; h < REP; ++h) {
-      if (lane == 0) {
-        s_m[wave][h] = m[h];
-        s_l[wave][h] = l[h];
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s_o[wave][h][c8 + i] = o[h][i];
-    }
-  }
-  __syncthreads();
-  const long long head0 = (long long)bk * REP;    // b * H + kvh * REP
-  for (int t = tid; t < REP * D; t += kThreads) {
-    const int h = t / D, d = t % D;
-    float mb = s_m[0][h];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) mb = fmaxf(mb, s_m[w][h]);
-    float lb = 0.f, ob = 0.f;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const float wt = exp2_fast(s_m[w][h] - mb);
-      lb = __fmaf_rn(s_l[w][h], wt, lb);
-      ob = __fmaf_rn(s_o[w][h][d], wt, ob);
-    }
-    const long long slot = (head0 + h) * n_split + split;
-    part_o[slot * D + d] = ob;
-    if (d == 0) {
-      part_ml[slot * 2] = mb;
-      part_ml[slot * 2 + 1] = lb;
-    }
+  for (int i = 0; i < E / 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
   }
 }
+
+// attn_decode_kernel for an e4m3 cache (acco_kv_append_fp8): codes of one
+// byte, row value = code * scale with k_scale / v_scale fp32 [B, Hkv, Smax].
+// The bytes halve, so the lanes regroup: a 16-byte load holds E = 16 dims,
+// D / 16 adjacent lanes own one key and a wave covers 1024 / D keys per step.
+// A lane then holds 16 dims of q and of o per head, 32 * REP registers: up to
+// REP = 3 that fits the 256 VGPRs, from REP = 4 it does not (the compiler
+// parks the rest in AGPRs and, at REP = 8, in scratch), so those group sizes
+// take E = 8 dims per lane by 8-byte loads, the lane layout and register
+// budget of the bf16 kernel. Each lane group also loads its key's two scales
+// (one address in all its lanes). The K scale multiplies the finished dot, s = (q . codes) * k_scale
+// * scale_log2; the V scale is folded into p once per key, o += (p * v_scale)
+// * code. Two steps in flight, the same online softmax, splits, workspace and
+// finish as above; no row at or beyond L is loaded, codes or scale.
+template <int D, int REP, int E = (REP <= 3 ? 16 : 8)>
+__global__ __launch_bounds__(kThreads)
+void attn_decode_fp8_kernel(const u16* __restrict__ q,
+                            const unsigned char* __restrict__ k_cache,
+                            const unsigned char* __restrict__ v_cache,
+                            const float* __restrict__ k_scale,
+                            const float* __restrict__ v_scale,
+                            const int* __restrict__ cache_len,
+                            float* __restrict__ part_ml,
+                            float* __restrict__ part_o, int Hkv, int Smax,
+                            int window, int chunk, float scale_log2,
+                            long long q_rs) {
+  using Raw = typename std::conditional<E == 16, uint4, uint2>::type;
+  constexpr int G = D / E;            // lanes per key row
+  constexpr int NG = kThreads / G;    // key rows per block step
+  const int split = blockIdx.x, n_split = gridDim.x;
+  const int bk = blockIdx.y;          // b * Hkv + kv head
+  const int b = bk / Hkv, kvh = bk % Hkv;
+  const int tid = threadIdx.x;
+  const int g = tid / G, ce = (tid % G) * E;
+
+  const int L = min(max(cache_len[b], 0), Smax);
+  const int lo = window > 0 ? max(L - window, 0) : 0;
+  const long long c0 = (long long)split * chunk;
+  const int start = (int)max((long long)lo, min(c0, (long long)L));
+  const int end = (int)min((long long)L, c0 + chunk);
+
+  float qf[REP][E];
+  const u16* qp = q + (long long)b * q_rs + (long long)kvh * REP * D + ce;
+#pragma unroll
+  for (int h = 0; h < REP; ++h)
+#pragma unroll
+    for (int i = 0; i < E; i += 8)
+      unpack8(*reinterpret_cast<const uint4*>(qp + h * D + i), qf[h] + i);
+
+  float m[REP], l[REP], o[REP][E];
+#pragma unroll
+  for (int h = 0; h < REP; ++h) {
+    m[h] = kNegBig;
+    l[h] = 0.f;
+#pragma unroll
+    for (int i = 0; i < E; ++i) o[h][i] = 0.f;
+  }
+
+  const long long srow = (long long)bk * Smax;    // first scale of the pair
+  const long long base = srow * D + ce;
+  auto step = [&](const Raw& kraw, const Raw& vraw, float ks, float vs) {
+    float kf[E], vf[E];
+    unpack_fp8<E>(kraw, kf);
+    unpack_fp8<E>(vraw, vf);
+    const float kss = ks * scale_log2;
+#pragma unroll
+    for (int h = 0; h < REP; ++h) {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < E; ++i) a = __fmaf_rn(qf[h][i], kf[i], a);
+#pragma unroll
+      for (int off = G / 2; off > 0; off >>= 1) a += __shfl_xor(a, off);
+      const float s = a * kss;
+      const float m_new = fmaxf(m[h], s);
+      const float alpha = exp2_fast(m[h] - m_new);
+      const float p = exp2_fast(s - m_new);
+      m[h] = m_new;
+      l[h] = __fmaf_rn(l[h], alpha, p);
+      const float pv = p * vs;
+#pragma unroll
+      for (int i = 0; i < E; ++i)
+        o[h][i] = __fmaf_rn(o[h][i], alpha, pv * vf[i]);
+    }
+  };
+
+  // every j below satisfies start <= j < end <= L <= Smax
+  int j = start + g;
+  for (; j + NG < end; j += 2 * NG) {
+    const long long r0 = base + (long long)j * D;
+    const long long r1 = r0 + (long long)NG * D;
+    const Raw k0 = *reinterpret_cast<const Raw*>(k_cache + r0);
+    const Raw k1 = *reinterpret_cast<const Raw*>(k_cache + r1);
+    const Raw v0 = *reinterpret_cast<const Raw*>(v_cache + r0);
+    const Raw v1 = *reinterpret_cast<const Raw*>(v_cache + r1);
+    const float ks0 = k_scale[srow + j], ks1 = k_scale[srow + j + NG];
+    const float vs0 = v_scale[srow + j], vs1 = v_scale[srow + j + NG];
+    step(k0, v0, ks0, vs0);
+    step(k1, v1, ks1, vs1);
+  }
+  if (j < end) {
+    const long long r0 = base + (long long)j * D;
+    const Raw k0 = *reinterpret_cast<const Raw*>(k_cache + r0);
+    const Raw v0 = *reinterpret_cast<const Raw*>(v_cache + r0);
+    step(k0, v0, k_scale[srow + j], v_scale[srow + j]);
+  }
+
+  decode_finish<D, REP, E>(m, l, o, ce, bk, split, n_split, part_ml, part_o);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
 
 // o[row, :] = sum_i exp2(m_i - M) o_i / sum_i exp2(m_i - M) l_i over the
 // splits i in order; l = 0 (no key at all) stores 0. One block per row of o
@@ -228,6 +385,27 @@ void launch_decode(int rep, dim3 grid, hipStream_t stream, const u16* q,
     hipLaunchKernelGGL((attn_decode_kernel<D, R>), grid, dim3(kThreads), 0,  \
                        stream, q, kc, vc, len, ml, po, Hkv, Smax, window,    \
                        chunk, scale_log2, q_rs);                             \
+    break;
+  switch (rep) {
+    ACCO_DECODE_REP(1) ACCO_DECODE_REP(2) ACCO_DECODE_REP(3)
+    ACCO_DECODE_REP(4) ACCO_DECODE_REP(5) ACCO_DECODE_REP(6)
+    ACCO_DECODE_REP(7) ACCO_DECODE_REP(8)
+    default: break;   // the binding admits 1 <= rep <= 8 only
+  }
+#undef ACCO_DECODE_REP
+}
+
+template <int D>
+void launch_decode_fp8(int rep, dim3 grid, hipStream_t stream, const u16* q,
+                       const unsigned char* kc, const unsigned char* vc,
+                       const float* ks, const float* vs, const int* len,
+                       float* ml, float* po, int Hkv, int Smax, int window,
+                       int chunk, float scale_log2, long long q_rs) {
+#define ACCO_DECODE_REP(R)                                                   \
+  case R:                                                                    \
+    hipLaunchKernelGGL((attn_decode_fp8_kernel<D, R>), grid,                 \
+                       dim3(kThreads), 0, stream, q, kc, vc, ks, vs, len,    \
+                       ml, po, Hkv, Smax, window, chunk, scale_log2, q_rs);  \
     break;
   switch (rep) {
     ACCO_DECODE_REP(1) ACCO_DECODE_REP(2) ACCO_DECODE_REP(3)
@@ -274,6 +452,33 @@ extern "C" void acco_attn_decode(const void* q, const void* k_cache,
     launch_decode<128>(H / Hkv, grid, stream, (const u16*)q,
                        (const u16*)k_cache, (const u16*)v_cache, cache_len,
                        ml, po, Hkv, Smax, window, chunk, scale_log2, q_rs);
+  acco_attn_split_combine(ml, po, o, (long long)B * H, n_split, D, stream);
+}
+
+extern "C" void acco_attn_decode_fp8(const void* q, const void* k_cache,
+                                     const void* v_cache,
+                                     const float* k_scale,
+                                     const float* v_scale,
+                                     const int* cache_len, void* o,
+                                     float* workspace, int B, int H, int Hkv,
+                                     int D, int Smax, float scale, int window,
+                                     long long q_rs, hipStream_t stream) {
+  int n_split, chunk;
+  acco_attn_decode_grid((long long)B * Hkv, Smax, &n_split, &chunk);
+  float* ml = workspace;
+  float* po = workspace + (long long)B * H * n_split * 2;
+  const dim3 grid(n_split, B * Hkv);
+  const float scale_log2 = scale * kLog2e;
+  const auto* kc = (const unsigned char*)k_cache;
+  const auto* vc = (const unsigned char*)v_cache;
+  if (D == 64)
+    launch_decode_fp8<64>(H / Hkv, grid, stream, (const u16*)q, kc, vc,
+                          k_scale, v_scale, cache_len, ml, po, Hkv, Smax,
+                          window, chunk, scale_log2, q_rs);
+  else
+    launch_decode_fp8<128>(H / Hkv, grid, stream, (const u16*)q, kc, vc,
+                           k_scale, v_scale, cache_len, ml, po, Hkv, Smax,
+                           window, chunk, scale_log2, q_rs);
   acco_attn_split_combine(ml, po, o, (long long)B * H, n_split, D, stream);
 }
 

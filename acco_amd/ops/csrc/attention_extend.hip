@@ -42,10 +42,18 @@
 //     workspace, no hand-off, the same bits on every run. One split writes
 //     bf16 o directly.
 //
+// attn_extend_kernel<D, true> reads an e4m3 cache (one-byte codes and one fp32
+// scale per row, acco_kv_append_fp8). Every e4m3 value is exactly a bf16
+// value, so the staging widens the codes into the same LDS tiles and both
+// products stay bf16 MFMAs; the row scales ride in 512 more bytes of LDS and
+// enter as two multiplies (the kernel's comment has the places).
+//
 // Two guesses nobody has measured: the column block (128 columns = 4 waves of
 // 32; with T * rep <= 32 three of the waves only help staging), and the split
 // count, which is acco_attn_decode_grid's rule applied to B * Hkv * column
 // blocks (about 512 workgroups, at least 256 keys per split, at most 64).
+
+#include <type_traits>
 
 #include "attention_common.h"
 #include "kernels.h"
@@ -103,6 +111,60 @@ ACCO_DEV void stage_transposed_edge(const u16* base, int row0, int row_max,
   }
 }
 
+// ---- staging of an e4m3 cache. Every e4m3 value is exactly a bf16 value, so
+// the tiles in LDS, and with them both products, stay bf16: a 16-byte load
+// holds 16 dims, v_cvt_pk_f32_fp8 widens them and the upper halves of the
+// floats are the 16 bf16 bit patterns. EDGE carries the rules of the two
+// helpers above: row index clamped to row_max, a row past it zero-filled.
+using u8 = unsigned char;
+
+template <bool EDGE>
+ACCO_DEV void load16_fp8(const u8* base, int row, int row_max, int D, int d0,
+                         u16* out) {
+  uint4 x = *reinterpret_cast<const uint4*>(
+      base + (long long)(EDGE ? min(row, row_max) : row) * D + d0);
+  if (EDGE && row > row_max) x = make_uint4(0, 0, 0, 0);
+  const int* w = reinterpret_cast<const int*>(&x);
+  unsigned* o2 = reinterpret_cast<unsigned*>(out);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
+    o2[2 * i] = (__float_as_uint(lo[0]) >> 16) |
+                (__float_as_uint(lo[1]) & 0xffff0000u);
+    o2[2 * i + 1] = (__float_as_uint(hi[0]) >> 16) |
+                    (__float_as_uint(hi[1]) & 0xffff0000u);
+  }
+}
+
+template <int D, bool EDGE>
+ACCO_DEV void stage_rowmajor_fp8(const u8* base, int row0, int row_max,
+                                 u16* dst) {
+  for (int c = threadIdx.x; c < TILE * (D / 16); c += kThreads) {
+    const int r = c / (D / 16), dc = c % (D / 16);
+    __attribute__((aligned(16))) u16 x[16];
+    load16_fp8<EDGE>(base, row0 + r, row_max, D, dc * 16, x);
+    uint4* d = reinterpret_cast<uint4*>(dst + r * (D + 8) + dc * 16);
+    d[0] = reinterpret_cast<const uint4*>(x)[0];
+    d[1] = reinterpret_cast<const uint4*>(x)[1];
+  }
+}
+
+template <int D, bool EDGE>
+ACCO_DEV void stage_transposed_fp8(const u8* base, int row0, int row_max,
+                                   u16* dst) {
+  const int r2 = (threadIdx.x & 31) * 2;            // tile row pair
+  for (int dg = threadIdx.x >> 5; dg < D / 16; dg += kThreads / 32) {
+    __attribute__((aligned(16))) u16 av[16], bv[16];
+    load16_fp8<EDGE>(base, row0 + r2, row_max, D, dg * 16, av);
+    load16_fp8<EDGE>(base, row0 + r2 + 1, row_max, D, dg * 16, bv);
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      *reinterpret_cast<ushort2*>(dst + (dg * 16 + i) * LST + r2) =
+          make_ushort2(av[i], bv[i]);
+  }
+}
+
 // lowest key of a query at position p
 ACCO_DEV int win_lo(int p, int window) {
   return window > 0 ? max(p + 1 - window, 0) : 0;
@@ -110,11 +172,23 @@ ACCO_DEV int win_lo(int p, int window) {
 
 // workspace layout, fp32: ml [B*T*H, n_split, 2] then o [B*T*H, n_split, D]
 // (rows in the order of o [B, T, H]); unused when gridDim.x == 1
-template <int D>
+//
+// FP8: the caches hold e4m3 codes (Elem = one byte) with one fp32 scale per
+// row, k_scale / v_scale [B, Hkv, Smax] (acco_kv_append_fp8). The tile's 64 K
+// and 64 V scales go to LDS after the tiles, with the clamp of the edge
+// staging (a row past row_max gets scale 0, never what the cache holds
+// there); the K scale multiplies the score of its key row with scale2, the V
+// scale multiplies P of its key row before it is rounded to bf16, and l sums
+// the unscaled P. Without FP8 the scale pointers are unused.
+template <int D, bool FP8>
 __global__ __launch_bounds__(kThreads)
 void attn_extend_kernel(const u16* __restrict__ q,
-                        const u16* __restrict__ k_cache,
-                        const u16* __restrict__ v_cache,
+                        const typename std::conditional<FP8, u8, u16>::type*
+                            __restrict__ k_cache,
+                        const typename std::conditional<FP8, u8, u16>::type*
+                            __restrict__ v_cache,
+                        const float* __restrict__ k_scale,
+                        const float* __restrict__ v_scale,
                         const int* __restrict__ cache_len,
                         u16* __restrict__ o, float* __restrict__ part_ml,
                         float* __restrict__ part_o, int T, int H, int Hkv,
@@ -137,6 +211,8 @@ void attn_extend_kernel(const u16* __restrict__ q,
   extern __shared__ __attribute__((aligned(16))) u16 smem[];
   u16* k_lds = smem + ExtendLds<D>::k_row;   // [TILE][D+8]
   u16* v_lds = smem + ExtendLds<D>::v_t;     // V^T: [D][LST]
+  // FP8: K scales [TILE] then V scales [TILE] of the staged tile
+  float* sc_lds = reinterpret_cast<float*>(smem + ExtendLds<D>::scales);
 
   // ---- the lane's column: token t, head hr of the group, keys [lo_q, hi_q]
   const int c = col0 + wave * 32 + lq;
@@ -175,8 +251,8 @@ void attn_extend_kernel(const u16* __restrict__ q,
   const int lo_w0 = win_lo(pw0, window), lo_w1 = win_lo(pw1, window);
   const bool ragged = cw0 + 31 >= ncols || L0 + tw1 >= Smax;  // a dead lane
 
-  const u16* Kb = k_cache + (long long)bk * Smax * D;
-  const u16* Vb = v_cache + (long long)bk * Smax * D;
+  const auto* Kb = k_cache + (long long)bk * Smax * D;
+  const auto* Vb = v_cache + (long long)bk * Smax * D;
 
   float m_c = kNegBig, l_c = 0.0f;     // per column lq (dup over hi)
   f32x16 acc_o[DT] = {};
@@ -185,7 +261,21 @@ void attn_extend_kernel(const u16* __restrict__ q,
   for (int j = j_lo; j <= j_hi; ++j) {
     const int row0 = j * TILE;
     __syncthreads();
-    if (row0 + TILE - 1 <= row_max) {
+    if constexpr (FP8) {
+      if (row0 + TILE - 1 <= row_max) {
+        stage_rowmajor_fp8<D, false>(Kb, row0, row_max, k_lds);
+        stage_transposed_fp8<D, false>(Vb, row0, row_max, v_lds);
+      } else {
+        stage_rowmajor_fp8<D, true>(Kb, row0, row_max, k_lds);
+        stage_transposed_fp8<D, true>(Vb, row0, row_max, v_lds);
+      }
+      if (threadIdx.x < 2 * TILE) {
+        const int row = row0 + (threadIdx.x & (TILE - 1));
+        const float* sp = (threadIdx.x < TILE ? k_scale : v_scale) +
+                          (long long)bk * Smax;
+        sc_lds[threadIdx.x] = row <= row_max ? sp[row] : 0.0f;
+      }
+    } else if (row0 + TILE - 1 <= row_max) {
       stage_rowmajor<D, kThreads>(Kb + (long long)row0 * D, D, k_lds);
       stage_transposed<D, kThreads>(Vb + (long long)row0 * D, D, v_lds);
     } else {
@@ -218,6 +308,19 @@ void attn_extend_kernel(const u16* __restrict__ q,
     // predicates.
     const bool need_mask =
         ragged || row0 + TILE - 1 > pw0 || row0 < lo_w1;
+    // FP8: the scales of the lane's 32 C rows, K now and V after the softmax
+    // (rows c32_row(4g .. 4g + 3, hi) are 4 adjacent floats)
+    float sc[32];
+    auto load_scales = [&](const float* src) {
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        const float4 a = *reinterpret_cast<const float4*>(
+            src + (g >> 2) * 32 + (g & 3) * 8 + 4 * hi);
+        sc[4 * g] = a.x, sc[4 * g + 1] = a.y;
+        sc[4 * g + 2] = a.z, sc[4 * g + 3] = a.w;
+      }
+    };
+    if constexpr (FP8) load_scales(sc_lds);
     float p[32];
     float tmax = kNegBig;
 #pragma unroll
@@ -226,6 +329,7 @@ void attn_extend_kernel(const u16* __restrict__ q,
       for (int r = 0; r < 16; ++r) {
         const int kv_g = row0 + m32 * 32 + c32_row(r, hi);
         float x = st[m32][r] * scale2;
+        if constexpr (FP8) x = st[m32][r] * (sc[m32 * 16 + r] * scale2);
         if (need_mask) x = (kv_g >= lo_q && kv_g <= hi_q) ? x : kNegBig;
         p[m32 * 16 + r] = x;
         tmax = fmaxf(tmax, x);
@@ -257,6 +361,11 @@ void attn_extend_kernel(const u16* __restrict__ q,
     }
     rsum += __shfl_xor(rsum, 32, 64);
     l_c += rsum;
+    if constexpr (FP8) {
+      load_scales(sc_lds + TILE);
+#pragma unroll
+      for (int i = 0; i < 32; ++i) p[i] *= sc[i];
+    }
 
     // ---- P (C layout) -> A fragments in registers, then PV
     __builtin_amdgcn_s_setprio(1);
@@ -323,12 +432,14 @@ extern "C" void acco_attn_extend_grid(long long BHkv, long long cols,
   *n_blk = (int)nb;
 }
 
-extern "C" void acco_attn_extend(const void* q, const void* k_cache,
-                                 const void* v_cache, const int* cache_len,
-                                 void* o, float* workspace, int B, int T,
-                                 int H, int Hkv, int D, int Smax, float scale,
-                                 int window, long long q_rs,
-                                 hipStream_t stream) {
+namespace {
+
+// both entry points: k_scale == nullptr is the bf16 cache
+void launch_extend(const void* q, const void* k_cache, const void* v_cache,
+                   const float* k_scale, const float* v_scale,
+                   const int* cache_len, void* o, float* workspace, int B,
+                   int T, int H, int Hkv, int D, int Smax, float scale,
+                   int window, long long q_rs, hipStream_t stream) {
   const int rep = H / Hkv;
   int n_blk, n_split, chunk;
   acco_attn_extend_grid((long long)B * Hkv, (long long)T * rep, Smax, &n_blk,
@@ -338,14 +449,45 @@ extern "C" void acco_attn_extend(const void* q, const void* k_cache,
   float* po = n_split > 1 ? workspace + rows * n_split * 2 : nullptr;
   const dim3 grid(n_split, B * Hkv, n_blk);
   const float scale2 = scale * 1.4426950408889634f;   // log2 domain
-#define ACCO_EXTEND(DD)                                                       \
-  hipLaunchKernelGGL((attn_extend_kernel<DD>), grid, dim3(kThreads),          \
-                     ExtendLds<DD>::bytes, stream, (const u16*)q,             \
-                     (const u16*)k_cache, (const u16*)v_cache, cache_len,     \
-                     (u16*)o, ml, po, T, H, Hkv, rep, Smax, window,           \
-                     chunk / TILE, scale2, q_rs)
-  if (D == 64) ACCO_EXTEND(64); else ACCO_EXTEND(128);
+#define ACCO_EXTEND(DD, FP8, ELEM, BYTES)                                     \
+  hipLaunchKernelGGL((attn_extend_kernel<DD, FP8>), grid, dim3(kThreads),     \
+                     ExtendLds<DD>::BYTES, stream, (const u16*)q,             \
+                     (const ELEM*)k_cache, (const ELEM*)v_cache, k_scale,     \
+                     v_scale, cache_len, (u16*)o, ml, po, T, H, Hkv, rep,     \
+                     Smax, window, chunk / TILE, scale2, q_rs)
+  if (k_scale == nullptr) {
+    if (D == 64) ACCO_EXTEND(64, false, u16, bytes);
+    else ACCO_EXTEND(128, false, u16, bytes);
+  } else {
+    if (D == 64) ACCO_EXTEND(64, true, u8, bytes_fp8);
+    else ACCO_EXTEND(128, true, u8, bytes_fp8);
+  }
 #undef ACCO_EXTEND
   if (n_split > 1)
     acco_attn_split_combine(ml, po, o, rows, n_split, D, stream);
+}
+
+}  // namespace
+
+extern "C" void acco_attn_extend(const void* q, const void* k_cache,
+                                 const void* v_cache, const int* cache_len,
+                                 void* o, float* workspace, int B, int T,
+                                 int H, int Hkv, int D, int Smax, float scale,
+                                 int window, long long q_rs,
+                                 hipStream_t stream) {
+  launch_extend(q, k_cache, v_cache, nullptr, nullptr, cache_len, o,
+                workspace, B, T, H, Hkv, D, Smax, scale, window, q_rs, stream);
+}
+
+extern "C" void acco_attn_extend_fp8(const void* q, const void* k_cache,
+                                     const void* v_cache,
+                                     const float* k_scale,
+                                     const float* v_scale,
+                                     const int* cache_len, void* o,
+                                     float* workspace, int B, int T, int H,
+                                     int Hkv, int D, int Smax, float scale,
+                                     int window, long long q_rs,
+                                     hipStream_t stream) {
+  launch_extend(q, k_cache, v_cache, k_scale, v_scale, cache_len, o,
+                workspace, B, T, H, Hkv, D, Smax, scale, window, q_rs, stream);
 }

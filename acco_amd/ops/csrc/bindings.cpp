@@ -1010,11 +1010,34 @@ struct CacheShape { int B, Hkv, Smax, D; };
 // The argument contract of both cache entry points: k_cache and v_cache
 // contiguous CUDA bf16 [B, Hkv, Smax, D] on one device, 16-byte aligned,
 // D in {64, 128}; cache_len contiguous int32 [B] on that device (data: the
-// kernels clamp it into [0, Smax]).
+// kernels clamp it into [0, Smax]). With k_scale / v_scale (the _fp8 entry
+// points) the caches are float8_e4m3fn instead and the scales contiguous
+// fp32 [B, Hkv, Smax] on the same device.
 static CacheShape check_cache_args(const at::Tensor& k_cache,
                                    const at::Tensor& v_cache,
-                                   const at::Tensor& cache_len) {
-  CHECK_BF16_CONTIG(k_cache); CHECK_BF16_CONTIG(v_cache);
+                                   const at::Tensor& cache_len,
+                                   const at::Tensor* k_scale = nullptr,
+                                   const at::Tensor* v_scale = nullptr) {
+  if (k_scale == nullptr) {
+    CHECK_BF16_CONTIG(k_cache); CHECK_BF16_CONTIG(v_cache);
+  } else {
+    // the e4m3 cache: one-byte codes and an fp32 scale per cache row
+    for (const at::Tensor* c : {&k_cache, &v_cache})
+      TORCH_CHECK(c->is_cuda() && c->is_contiguous() &&
+                  c->scalar_type() == at::kFloat8_e4m3fn,
+                  "k_cache and v_cache must be contiguous CUDA float8_e4m3fn,"
+                  " got ", c->scalar_type(), " on ", c->device());
+    TORCH_CHECK(k_cache.dim() == 4, "k_cache must be [B, Hkv, Smax, D]");
+    for (const at::Tensor* s : {k_scale, v_scale})
+      TORCH_CHECK(s->is_cuda() && s->device() == k_cache.device() &&
+                  s->is_contiguous() && s->scalar_type() == at::kFloat &&
+                  s->dim() == 3 && s->size(0) == k_cache.size(0) &&
+                  s->size(1) == k_cache.size(1) &&
+                  s->size(2) == k_cache.size(2),
+                  "k_scale and v_scale must be contiguous fp32 [B, Hkv, Smax]"
+                  " on ", k_cache.device(), ", got ", s->scalar_type(), " ",
+                  s->sizes(), " on ", s->device());
+  }
   TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
               v_cache.device() == k_cache.device(),
               "k_cache and v_cache must be [B, Hkv, Smax, D] of one shape on "
@@ -1110,6 +1133,51 @@ c10::optional<at::Tensor> kv_append(c10::optional<at::Tensor> q, at::Tensor k,
   return q_out;
 }
 
+// kv_append into an e4m3 cache (codes + one fp32 scale per cache row): the
+// same arguments and checks, plus k_scale / v_scale fp32 [B, Hkv, Smax]
+c10::optional<at::Tensor> kv_append_fp8(
+    c10::optional<at::Tensor> q, at::Tensor k, at::Tensor v,
+    c10::optional<at::Tensor> cos_t, c10::optional<at::Tensor> sin_t,
+    at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
+    at::Tensor v_scale, at::Tensor cache_len) {
+  const auto [B, Hkv, Smax, D] =
+      check_cache_args(k_cache, v_cache, cache_len, &k_scale, &v_scale);
+  TORCH_CHECK(k.dim() == 4, "k must be [B, T, Hkv, D], got ", k.sizes());
+  const int64_t T = k.size(1);
+  TORCH_CHECK(T >= 0 && T < (1LL << 30), "k: T out of range: ", T);
+  const long long k_rs = check_token_rows(k, k_cache, B, T, Hkv, D, "k");
+  const long long v_rs = check_token_rows(v, k_cache, B, T, Hkv, D, "v");
+  TORCH_CHECK(cos_t.has_value() == sin_t.has_value(),
+              "cos and sin must both be given or both be None");
+  TORCH_CHECK(cos_t.has_value() == q.has_value(),
+              "q is rotated with the tables: give q, cos and sin, or none");
+  int64_t H = 0;
+  long long q_rs = 0;
+  c10::optional<at::Tensor> q_out;
+  if (cos_t.has_value()) {
+    TORCH_CHECK(q->dim() == 4 && q->size(2) > 0 && q->size(2) % Hkv == 0,
+                "q must be [B, T, H, D] with H % Hkv == 0, got ", q->sizes());
+    H = q->size(2);
+    q_rs = check_token_rows(*q, k_cache, B, T, H, D, "q");
+    check_rope_table(*cos_t, *sin_t, Smax, D, k_cache);
+    TORCH_CHECK(cos_t->size(0) < (1LL << 31), "cos: too many rows");
+    q_out = at::empty({B, T, H, D}, q->options());
+  }
+  TORCH_CHECK((long long)B * T * (H + 2 * Hkv) * (D / 16) < (1LL << 31),
+              "k: too many elements for one launch");
+  if (T == 0) return q_out;
+  acco_kv_append_fp8(
+      q_out ? q->data_ptr() : nullptr, k.data_ptr(), v.data_ptr(),
+      q_out ? q_out->data_ptr() : nullptr, k_cache.data_ptr(),
+      v_cache.data_ptr(), k_scale.data_ptr<float>(),
+      v_scale.data_ptr<float>(), cache_len.data_ptr<int>(),
+      q_out ? cos_t->data_ptr<float>() : nullptr,
+      q_out ? sin_t->data_ptr<float>() : nullptr, B, (int)T, (int)H, Hkv, D,
+      Smax, q_out ? (int)cos_t->size(0) : 0, q_rs, k_rs, v_rs, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return q_out;
+}
+
 // (n_split, chunk) of attn_decode for B*Hkv (sequence, kv head) pairs and a
 // cache of Smax rows: split i owns keys [i*chunk, (i+1)*chunk)
 std::vector<int64_t> attn_decode_grid(int64_t BHkv, int64_t Smax) {
@@ -1124,9 +1192,16 @@ std::vector<int64_t> attn_decode_grid(int64_t BHkv, int64_t Smax) {
 // o [B, H, D] of one query token per sequence: q [B, H, D] bf16 whose rows
 // may be strided (a section of the packed projection output). A window at or
 // beyond Smax bounds nothing and reaches the kernel as 0 (none).
-at::Tensor attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
-                       at::Tensor cache_len, double scale, int64_t window) {
-  const auto [B, Hkv, Smax, D] = check_cache_args(k_cache, v_cache, cache_len);
+// With k_scale / v_scale the caches are e4m3 (attn_decode_fp8 below).
+static at::Tensor attn_decode_any(const at::Tensor& q,
+                                  const at::Tensor& k_cache,
+                                  const at::Tensor& v_cache,
+                                  const at::Tensor* k_scale,
+                                  const at::Tensor* v_scale,
+                                  const at::Tensor& cache_len, double scale,
+                                  int64_t window) {
+  const auto [B, Hkv, Smax, D] =
+      check_cache_args(k_cache, v_cache, cache_len, k_scale, v_scale);
   TORCH_CHECK(q.dim() == 3, "q must be [B, H, D], got ", q.sizes());
   const int64_t H = q.size(1);
   TORCH_CHECK(H > 0 && H % Hkv == 0 && H / Hkv <= 8,
@@ -1138,15 +1213,37 @@ at::Tensor attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
   const int win = window >= Smax ? 0 : (int)window;
   int n_split, chunk;
   acco_attn_decode_grid((long long)B * Hkv, Smax, &n_split, &chunk);
-  auto o = at::empty({B, H, D}, k_cache.options());
+  auto o = at::empty({B, H, D}, q.options());
   auto ws = at::empty({(int64_t)B * H * n_split * (2 + D)},
-                      k_cache.options().dtype(at::kFloat));
-  acco_attn_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                   cache_len.data_ptr<int>(), o.data_ptr(),
-                   ws.data_ptr<float>(), B, (int)H, Hkv, D, Smax,
-                   (float)scale, win, q_rs, cur_stream());
+                      q.options().dtype(at::kFloat));
+  if (k_scale == nullptr)
+    acco_attn_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                     cache_len.data_ptr<int>(), o.data_ptr(),
+                     ws.data_ptr<float>(), B, (int)H, Hkv, D, Smax,
+                     (float)scale, win, q_rs, cur_stream());
+  else
+    acco_attn_decode_fp8(q.data_ptr(), k_cache.data_ptr(),
+                         v_cache.data_ptr(), k_scale->data_ptr<float>(),
+                         v_scale->data_ptr<float>(),
+                         cache_len.data_ptr<int>(), o.data_ptr(),
+                         ws.data_ptr<float>(), B, (int)H, Hkv, D, Smax,
+                         (float)scale, win, q_rs, cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return o;
+}
+
+at::Tensor attn_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
+                       at::Tensor cache_len, double scale, int64_t window) {
+  return attn_decode_any(q, k_cache, v_cache, nullptr, nullptr, cache_len,
+                         scale, window);
+}
+
+at::Tensor attn_decode_fp8(at::Tensor q, at::Tensor k_cache,
+                           at::Tensor v_cache, at::Tensor k_scale,
+                           at::Tensor v_scale, at::Tensor cache_len,
+                           double scale, int64_t window) {
+  return attn_decode_any(q, k_cache, v_cache, &k_scale, &v_scale, cache_len,
+                         scale, window);
 }
 
 // T, H / Hkv and the element counts attn_extend's int arithmetic and grid take
@@ -1178,9 +1275,16 @@ std::vector<int64_t> attn_extend_grid(int64_t BHkv, int64_t cols,
 // already: q [B, T, H, D] bf16 whose token rows may be strided (a section of
 // the packed projection output); cache_len is the length before the T tokens.
 // A window at or beyond Smax bounds nothing and reaches the kernel as 0.
-at::Tensor attn_extend(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
-                       at::Tensor cache_len, double scale, int64_t window) {
-  const auto [B, Hkv, Smax, D] = check_cache_args(k_cache, v_cache, cache_len);
+// With k_scale / v_scale the caches are e4m3 (attn_extend_fp8 below).
+static at::Tensor attn_extend_any(const at::Tensor& q,
+                                  const at::Tensor& k_cache,
+                                  const at::Tensor& v_cache,
+                                  const at::Tensor* k_scale,
+                                  const at::Tensor* v_scale,
+                                  const at::Tensor& cache_len, double scale,
+                                  int64_t window) {
+  const auto [B, Hkv, Smax, D] =
+      check_cache_args(k_cache, v_cache, cache_len, k_scale, v_scale);
   TORCH_CHECK(q.dim() == 4, "q must be [B, T, H, D], got ", q.sizes());
   const int64_t T = q.size(1), H = q.size(2);
   check_extend_sizes(B, T, H, Hkv);
@@ -1190,16 +1294,38 @@ at::Tensor attn_extend(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
   int n_blk, n_split, chunk;
   acco_attn_extend_grid((long long)B * Hkv, T * (H / Hkv), Smax, &n_blk,
                         &n_split, &chunk);
-  auto o = at::empty({B, T, H, D}, k_cache.options());
+  auto o = at::empty({B, T, H, D}, q.options());
   auto ws = at::empty(
       {n_split > 1 ? (int64_t)B * T * H * n_split * (2 + D) : 0},
-      k_cache.options().dtype(at::kFloat));
-  acco_attn_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                   cache_len.data_ptr<int>(), o.data_ptr(),
-                   ws.data_ptr<float>(), B, (int)T, (int)H, Hkv, D, Smax,
-                   (float)scale, win, q_rs, cur_stream());
+      q.options().dtype(at::kFloat));
+  if (k_scale == nullptr)
+    acco_attn_extend(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                     cache_len.data_ptr<int>(), o.data_ptr(),
+                     ws.data_ptr<float>(), B, (int)T, (int)H, Hkv, D, Smax,
+                     (float)scale, win, q_rs, cur_stream());
+  else
+    acco_attn_extend_fp8(q.data_ptr(), k_cache.data_ptr(),
+                         v_cache.data_ptr(), k_scale->data_ptr<float>(),
+                         v_scale->data_ptr<float>(),
+                         cache_len.data_ptr<int>(), o.data_ptr(),
+                         ws.data_ptr<float>(), B, (int)T, (int)H, Hkv, D,
+                         Smax, (float)scale, win, q_rs, cur_stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return o;
+}
+
+at::Tensor attn_extend(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
+                       at::Tensor cache_len, double scale, int64_t window) {
+  return attn_extend_any(q, k_cache, v_cache, nullptr, nullptr, cache_len,
+                         scale, window);
+}
+
+at::Tensor attn_extend_fp8(at::Tensor q, at::Tensor k_cache,
+                           at::Tensor v_cache, at::Tensor k_scale,
+                           at::Tensor v_scale, at::Tensor cache_len,
+                           double scale, int64_t window) {
+  return attn_extend_any(q, k_cache, v_cache, &k_scale, &v_scale, cache_len,
+                         scale, window);
 }
 
 // ---- on-device sampling (sample.hip)
@@ -1275,6 +1401,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_append", &kv_append, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("cos"), py::arg("sin"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("cache_len"));
+  m.def("kv_append_fp8", &kv_append_fp8, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("cos"), py::arg("sin"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("cache_len"));
+  m.def("attn_decode_fp8", &attn_decode_fp8, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("cache_len"), py::arg("scale"),
+        py::arg("window"));
+  m.def("attn_extend_fp8", &attn_extend_fp8, py::arg("q"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("cache_len"), py::arg("scale"),
+        py::arg("window"));
   m.def("attn_decode_grid", &attn_decode_grid, py::arg("BHkv"),
         py::arg("Smax"));
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"),

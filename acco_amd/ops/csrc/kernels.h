@@ -80,6 +80,17 @@ void acco_kv_append(const void* q, const void* k, const void* v, void* q_out,
                     int H, int Hkv, int D, int Smax, int table_rows,
                     long long q_rs, long long k_rs, long long v_rs,
                     hipStream_t stream);
+// The same into an e4m3 cache: codes [B, Hkv, Smax, D] of one byte and one
+// fp32 scale per cache row, k_scale / v_scale [B, Hkv, Smax]; a row's value
+// is code * scale, scale = max |row| / 448 of the bf16 row the call above
+// would have stored. A dropped row writes neither codes nor scale.
+void acco_kv_append_fp8(const void* q, const void* k, const void* v,
+                        void* q_out, void* k_cache, void* v_cache,
+                        float* k_scale, float* v_scale, const int* cache_len,
+                        const float* cos_t, const float* sin_t, int B, int T,
+                        int H, int Hkv, int D, int Smax, int table_rows,
+                        long long q_rs, long long k_rs, long long v_rs,
+                        hipStream_t stream);
 
 // ---- attention_decode.hip
 // One query token per sequence against the cache: q [B, H, D] (row stride
@@ -94,7 +105,15 @@ void acco_attn_decode(const void* q, const void* k_cache, const void* v_cache,
                       const int* cache_len, void* o, float* workspace, int B,
                       int H, int Hkv, int D, int Smax, float scale,
                       int window, long long q_rs, hipStream_t stream);
-// The combine of both split kernels: o[row, :] bf16 from the fp32 partials
+// The same against an e4m3 cache with its row scales (acco_kv_append_fp8);
+// the same grid and workspace
+void acco_attn_decode_fp8(const void* q, const void* k_cache,
+                          const void* v_cache, const float* k_scale,
+                          const float* v_scale, const int* cache_len, void* o,
+                          float* workspace, int B, int H, int Hkv, int D,
+                          int Smax, float scale, int window, long long q_rs,
+                          hipStream_t stream);
+// The combine of all split kernels: o[row, :] bf16 from the fp32 partials
 // ml [rows, n_split, 2] and o [rows, n_split, D], in split order
 void acco_attn_split_combine(const float* part_ml, const float* part_o,
                              void* o, long long rows, int n_split, int D,
@@ -116,6 +135,14 @@ void acco_attn_extend(const void* q, const void* k_cache, const void* v_cache,
                       const int* cache_len, void* o, float* workspace, int B,
                       int T, int H, int Hkv, int D, int Smax, float scale,
                       int window, long long q_rs, hipStream_t stream);
+// The same against an e4m3 cache with its row scales (acco_kv_append_fp8);
+// the same grid and workspace
+void acco_attn_extend_fp8(const void* q, const void* k_cache,
+                          const void* v_cache, const float* k_scale,
+                          const float* v_scale, const int* cache_len, void* o,
+                          float* workspace, int B, int T, int H, int Hkv,
+                          int D, int Smax, float scale, int window,
+                          long long q_rs, hipStream_t stream);
 
 // ---- ce.hip
 // bf16 logits on a 16-byte aligned base (any V). A token is valid iff

@@ -6,7 +6,10 @@
 // Backward: rotation by -theta:  dx1 = dy1*cos + dy2*sin ;
 //           dx2 = dy2*cos - dy1*sin.
 // Also home of the KV-cache append of generation (kv_append_kernel), which
-// rotates K at its absolute position with the same rot8.
+// rotates K at its absolute position with the same rot8, and of its variant
+// for an e4m3 cache (kv_append_fp8_kernel), which quantises each appended row
+// in the same launch: one fp32 scale per (token, kv head) from the row's own
+// maximum, codes by v_cvt_pk_fp8_f32.
 
 #include "common.h"
 #include "kernels.h"
@@ -167,7 +170,130 @@ void kv_append_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
   *reinterpret_cast<uint4*>(dst + D / 2) = v2;
 }
 
+// New device code is built without the packed fp32 VALU ops (see
+// attention_extend.hip); the kernels above keep the build they were measured
+// with. The host pass does not know the feature, hence the guard.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                      \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+
+// 8 values -> 8 OCP e4m3 codes (v_cvt_pk_fp8_f32: round to nearest even,
+// subnormals kept); the inputs are already inside [-448, 448]
+ACCO_DEV uint2 quant8(const u16* x, float inv) {
+  float y[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    y[k] = fminf(fmaxf(__fmul_rn(bf16_to_f32(x[k]), inv), -448.0f), 448.0f);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+  return make_uint2((unsigned)lo, (unsigned)hi);
+}
+
+// kv_append_kernel for an e4m3 cache: codes [B, Hkv, Smax, D] of one byte and
+// one fp32 scale per cache row, k_scale / v_scale [B, Hkv, Smax]. The same
+// work split, clamping, drop rule and rotated q_out. A K or V row is
+// quantised from the bf16 bits the bf16 append would have stored (K after the
+// rotation, rounded to bf16): amax = max |x|, scale = amax / 448, inv =
+// amax > 0 ? 448 / amax : 0, code = e4m3(clamp(x * inv, -448, 448)), every
+// step one rounded fp32 operation (torch_ref.kv_quantize is the definition).
+// The D / 16 lanes of a row are adjacent and aligned in one wave (ipt and 256
+// are multiples of cph) and reduce amax by xor shuffles. No lane leaves
+// before the shuffle except past `total`, a multiple of cph: a dropped row
+// shuffles like a live one and only skips its stores.
+__global__ __launch_bounds__(256)
+void kv_append_fp8_kernel(const u16* __restrict__ q, const u16* __restrict__ k,
+                          const u16* __restrict__ v, u16* __restrict__ q_out,
+                          unsigned char* __restrict__ k_cache,
+                          unsigned char* __restrict__ v_cache,
+                          float* __restrict__ k_scale,
+                          float* __restrict__ v_scale,
+                          const int* __restrict__ cache_len,
+                          const float* __restrict__ cos_t,
+                          const float* __restrict__ sin_t, unsigned total,
+                          unsigned T, unsigned Hq, unsigned Hkv, unsigned D,
+                          int Smax, int rows, long long q_rs, long long k_rs,
+                          long long v_rs) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= total) return;                       // whole lane groups
+  const unsigned cph = D / 16;                  // 8-pair chunks per head
+  const unsigned ipt = (Hq + 2 * Hkv) * cph;    // items per token
+  const unsigned tok = i / ipt, r = i % ipt;
+  const unsigned b = tok / T, t = tok % T;
+  const unsigned hh = r / cph, c8 = (r % cph) * 8;
+  const int len = min(max(cache_len[b], 0), Smax);
+  const long long p = (long long)len + t;       // absolute position
+  const bool is_q = hh < Hq, is_k = !is_q && hh < Hq + Hkv;
+  const bool live = is_q || p < Smax;           // else dropped, never written
+  const unsigned h = is_q ? hh : (is_k ? hh - Hq : hh - Hq - Hkv);
+  const u16* src = is_q ? q + (long long)tok * q_rs
+                 : is_k ? k + (long long)tok * k_rs
+                        : v + (long long)tok * v_rs;
+  src += (long long)h * D + c8;
+  uint4 v1 = *reinterpret_cast<const uint4*>(src);
+  uint4 v2 = *reinterpret_cast<const uint4*>(src + D / 2);
+  if (cos_t != nullptr && (is_q || is_k)) {
+    const size_t row = (size_t)min(p, (long long)rows - 1);
+    const float4* cp = reinterpret_cast<const float4*>(cos_t + row * D + c8);
+    const float4* sp = reinterpret_cast<const float4*>(sin_t + row * D + c8);
+    const float4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
+    const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    const float ss[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    rot8(v1, v2, cc, ss);
+  }
+  const u16* a = reinterpret_cast<const u16*>(&v1);
+  const u16* bq = reinterpret_cast<const u16*>(&v2);
+  float amax = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    amax = fmaxf(amax, fmaxf(fabsf(bf16_to_f32(a[e])),
+                             fabsf(bf16_to_f32(bq[e]))));
+  // every lane below `total` is here: q rows and dropped rows shuffle too
+  for (unsigned off = cph / 2; off > 0; off >>= 1)
+    amax = fmaxf(amax, __shfl_xor(amax, (int)off));
+  if (!live) return;
+  if (is_q) {
+    u16* dst = q_out + ((long long)tok * Hq + h) * D + c8;
+    *reinterpret_cast<uint4*>(dst) = v1;
+    *reinterpret_cast<uint4*>(dst + D / 2) = v2;
+    return;
+  }
+  const float inv = amax > 0.f ? __fdiv_rn(448.0f, amax) : 0.f;
+  const long long row = ((long long)b * Hkv + h) * Smax + p;
+  unsigned char* dst = (is_k ? k_cache : v_cache) + row * D + c8;
+  *reinterpret_cast<uint2*>(dst) = quant8(a, inv);
+  *reinterpret_cast<uint2*>(dst + D / 2) = quant8(bq, inv);
+  if (c8 == 0) (is_k ? k_scale : v_scale)[row] = __fdiv_rn(amax, 448.0f);
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 }  // namespace
+
+extern "C" void acco_kv_append_fp8(const void* q, const void* k, const void* v,
+                                   void* q_out, void* k_cache, void* v_cache,
+                                   float* k_scale, float* v_scale,
+                                   const int* cache_len, const float* cos_t,
+                                   const float* sin_t, int B, int T, int H,
+                                   int Hkv, int D, int Smax, int table_rows,
+                                   long long q_rs, long long k_rs,
+                                   long long v_rs, hipStream_t stream) {
+  const int Hq = (cos_t != nullptr && q != nullptr) ? H : 0;
+  const unsigned total = (unsigned)((long long)B * T * (Hq + 2 * Hkv) *
+                                    (D / 16));
+  if (total == 0) return;
+  hipLaunchKernelGGL(kv_append_fp8_kernel, dim3((total + 255) / 256),
+                     dim3(256), 0, stream, (const u16*)q, (const u16*)k,
+                     (const u16*)v, (u16*)q_out, (unsigned char*)k_cache,
+                     (unsigned char*)v_cache, k_scale, v_scale, cache_len,
+                     cos_t, sin_t, total, (unsigned)T, (unsigned)Hq,
+                     (unsigned)Hkv, (unsigned)D, Smax, table_rows, q_rs, k_rs,
+                     v_rs);
+}
 
 extern "C" void acco_kv_append(const void* q, const void* k, const void* v,
                                void* q_out, void* k_cache, void* v_cache,

@@ -155,19 +155,57 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 # cache_len is data: it is clamped into [0, Smax] and otherwise only
 # compared, the convention of the document-mask arrays. No host sync.
 
+#
+# FP8 cache: k / v hold OCP e4m3 codes (torch.float8_e4m3fn: max 448, no inf)
+# and k_scale / v_scale [B, Hkv, Smax] fp32 hold one scale per cache row; a
+# row's value is float(code) * scale. kv_quantize / kv_dequantize are the
+# executable definition of the format; the HIP kernels match kv_quantize bit
+# for bit on IEEE fp32 arithmetic (the CPU).
+
+E4M3_MAX = 448.0
+
+
+def kv_quantize(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(codes e4m3 [..., D], scale fp32 [...]) of rows x [..., D]. Every step
+    is one rounded fp32 operation: amax = max |x|, scale = amax / 448, inv =
+    448 / amax (0 for a zero row), y = clamp(x * inv, -448, 448), code =
+    round-to-nearest-even e4m3(y), subnormals kept. The row maximum maps to
+    +-448 exactly; a zero row gives scale 0 and zero codes."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    top = torch.full_like(amax, E4M3_MAX)
+    scale = amax / top
+    # a true division, not Tensor.__rtruediv__'s reciprocal-and-multiply
+    inv = torch.where(amax > 0, top / amax, torch.zeros_like(amax))
+    y = (xf * inv[..., None]).clamp(-E4M3_MAX, E4M3_MAX)
+    return y.to(torch.float8_e4m3fn), scale
+
+
+def kv_dequantize(codes: torch.Tensor, scale: torch.Tensor,
+                  dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """float(code) * scale per row, computed and returned in `dtype`."""
+    return codes.to(dtype) * scale.to(dtype)[..., None]
+
+
 @torch.no_grad()
 def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
               cache_len: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               q: Optional[torch.Tensor] = None,
               cos: Optional[torch.Tensor] = None,
-              sin: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+              sin: Optional[torch.Tensor] = None,
+              k_scale: Optional[torch.Tensor] = None,
+              v_scale: Optional[torch.Tensor] = None
+              ) -> Optional[torch.Tensor]:
     """Write k, v [B, T, Hkv, D] of T new tokens per sequence into the caches,
     in place: token t of sequence b goes to row p = clamp(cache_len[b]) + t,
     and a row at or beyond Smax is dropped. With `cos` / `sin` ([>= Smax, D])
     K is rotated by row p, its absolute position, exactly as rope_apply
     rotates it in a full forward, and the rotated q [B, T, H, D] is returned
     (a dropped token's q takes the table's last row); without them K is copied
-    and None is returned. `cache_len` is not modified."""
+    and None is returned. `cache_len` is not modified. With `k_scale` /
+    `v_scale` the caches are e4m3: each new row (K after the rotation, in k's
+    dtype) goes through kv_quantize, its codes to the cache and its scale to
+    the same row of the scale tensor."""
     B, T, Hkv, D = k.shape
     Smax = k_cache.shape[2]
     base = cache_len.long().clamp(0, Smax)                      # [B]
@@ -186,16 +224,33 @@ def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
     t = torch.arange(Smax, device=k.device)[None, :] - base[:, None]
     take = ((t >= 0) & (t < T))[:, None, :, None]               # [B,1,Smax,1]
     idx = t.clamp(0, T - 1)[:, None, :, None].expand(B, Hkv, Smax, D)
-    for cache, new in ((k_cache, k), (v_cache, v)):
-        rows = new.permute(0, 2, 1, 3).gather(2, idx).to(cache.dtype)
-        cache.copy_(torch.where(take, rows, cache))
+    for cache, new, sc in ((k_cache, k, k_scale), (v_cache, v, v_scale)):
+        rows = new.permute(0, 2, 1, 3).gather(2, idx)
+        if sc is None:
+            cache.copy_(torch.where(take, rows.to(cache.dtype), cache))
+            continue
+        codes, scale = kv_quantize(rows)
+        # select on the bytes: torch.where has no float8 kernel everywhere
+        cache.view(torch.uint8).copy_(torch.where(
+            take, codes.view(torch.uint8), cache.view(torch.uint8)))
+        sc.copy_(torch.where(take[..., 0], scale, sc))
     return q_rot
+
+
+def _wide_cache(cache: torch.Tensor, row_scale: Optional[torch.Tensor],
+                wide: torch.dtype) -> torch.Tensor:
+    """The cache in the math dtype: dequantised when it has row scales."""
+    if row_scale is None:
+        return cache.to(wide)
+    return kv_dequantize(cache, row_scale, wide)
 
 
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, cache_len: torch.Tensor,
                      scale: Optional[float] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
+                     window: Optional[int] = None,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Attention of one query token per sequence against the cache.
 
     q [B, H, D] is the query of the LAST cached token, position L - 1 with
@@ -203,7 +258,8 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     (`window` None or 0 = no window; the convention of causal_attention:
     j > L - 1 - window). Rows at or beyond L are never used, whatever they
     hold. L = 0 gives zeros. Math in the wider of q's dtype and fp32; returns
-    [B, H, D] in q's dtype."""
+    [B, H, D] in q's dtype. With `k_scale` / `v_scale` the caches are e4m3
+    and are dequantised first (kv_dequantize), then the same math."""
     B, H, D = q.shape
     Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
     wide = torch.promote_types(q.dtype, torch.float32)
@@ -216,8 +272,8 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
         allow = allow & (j >= L - int(window))
     a4 = allow[:, None, :, None]
     zero = torch.zeros((), dtype=wide, device=q.device)
-    k = torch.where(a4, k_cache.to(wide), zero)
-    v = torch.where(a4, v_cache.to(wide), zero)
+    k = torch.where(a4, _wide_cache(k_cache, k_scale, wide), zero)
+    v = torch.where(a4, _wide_cache(v_cache, v_scale, wide), zero)
     if Hkv != H:
         k = k.repeat_interleave(H // Hkv, dim=1)
         v = v.repeat_interleave(H // Hkv, dim=1)
@@ -233,7 +289,9 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
 def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, cache_len: torch.Tensor,
                      scale: Optional[float] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
+                     window: Optional[int] = None,
+                     k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Attention of T new query tokens per sequence against the cache, which
     already holds their K / V (kv_append with the same `cache_len`).
 
@@ -244,7 +302,8 @@ def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
     p >= Smax (its token was dropped by the append) gives +0. Rows above the
     keys a query attends are never used, whatever they hold. Math in the
     wider of q's dtype and fp32; returns [B, T, H, D] in q's dtype. T = 1 is
-    decode_attention(q[:, 0], ..., cache_len + 1)."""
+    decode_attention(q[:, 0], ..., cache_len + 1). `k_scale` / `v_scale`: an
+    e4m3 cache, as in decode_attention."""
     B, T, H, D = q.shape
     Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
     wide = torch.promote_types(q.dtype, torch.float32)
@@ -259,8 +318,8 @@ def extend_attention(q: torch.Tensor, k_cache: torch.Tensor,
     # a row no query of the sequence attends is replaced before any arithmetic
     used = allow.any(1)[:, None, :, None]                         # [B,1,Smax,1]
     zero = torch.zeros((), dtype=wide, device=q.device)
-    k = torch.where(used, k_cache.to(wide), zero)
-    v = torch.where(used, v_cache.to(wide), zero)
+    k = torch.where(used, _wide_cache(k_cache, k_scale, wide), zero)
+    v = torch.where(used, _wide_cache(v_cache, v_scale, wide), zero)
     if Hkv != H:
         k = k.repeat_interleave(H // Hkv, dim=1)
         v = v.repeat_interleave(H // Hkv, dim=1)

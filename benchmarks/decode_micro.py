@@ -19,6 +19,11 @@ attention kernel alone.
    before it: T successive ops.decode_attention calls (T = 8), or the fp32
    reference math torch_ref.extend_attention (T = 256).
 
+4. Next to every row of 2 and 3 the same call on an e4m3 cache ("kv_dtype":
+   "fp8": codes of one byte and one fp32 scale per row, quantised from the
+   same random rows), same shapes, same method; its cache_bytes count the
+   codes and the scales. 1 gets a third run, use_cache on with the fp8 cache.
+
 Prints one JSON line per measurement. Needs a GPU: there is no CPU fallback.
 """
 
@@ -67,17 +72,19 @@ def bench_generate(preset, prompt_len, new_tokens, repeats):
 
     def run(use_cache):
         return generate(model, ids, new_tokens, 0.0, max_len,
-                        use_cache=use_cache)
+                        use_cache=bool(use_cache),
+                        kv_dtype=FP8 if use_cache == "fp8" else None)
 
-    for use_cache in (False, True):
+    variants = (False, True, "fp8")
+    for use_cache in variants:
         run(use_cache)                       # warm-up: every shape once
-    times = {False: [], True: []}
+    times = {v: [] for v in variants}
     for _ in range(repeats):
-        for use_cache in (False, True):
+        for use_cache in variants:
             sec, out = event_seconds(lambda: run(use_cache))
             assert out.shape[1] == prompt_len + new_tokens
             times[use_cache].append(sec / new_tokens)
-    for use_cache in (False, True):
+    for use_cache in variants:
         t = times[use_cache]
         print(json.dumps({
             "bench": "generate", "model": preset, "use_cache": use_cache,
@@ -86,15 +93,32 @@ def bench_generate(preset, prompt_len, new_tokens, repeats):
     return min(times[False]), min(times[True])
 
 
+FP8 = torch.float8_e4m3fn
+
+
+def _caches(shape, copies, fp8):
+    """`copies` random caches of `shape`: bf16 tensors, or (codes, scales)
+    pairs of the same rows for an e4m3 cache."""
+    rows = [torch.randn(shape, device="cuda", dtype=torch.bfloat16)
+            for _ in range(copies)]
+    return [ops.torch_ref.kv_quantize(r) for r in rows] if fp8 else rows
+
+
+def _scales(kc, vc):
+    """(k_cache, v_cache, keyword arguments) of one cache op call."""
+    if isinstance(kc, tuple):
+        return kc[0], vc[0], dict(k_scale=kc[1], v_scale=vc[1])
+    return kc, vc, {}
+
+
 def bench_decode_kernel(B, L, H=32, Hkv=8, D=64, calls=400,
-                        rotate_bytes=1 << 30):
+                        rotate_bytes=1 << 30, fp8=False):
     dev, dt = "cuda", torch.bfloat16
-    cache_bytes = 2 * B * Hkv * L * D * 2            # K and V, bf16
+    # K and V: bf16 rows, or one-byte codes and an fp32 scale per row
+    cache_bytes = 2 * B * Hkv * L * (D + 4 if fp8 else D * 2)
     copies = max(1, min(512, -(-rotate_bytes // cache_bytes)))
-    kcs = [torch.randn(B, Hkv, L, D, device=dev, dtype=dt)
-           for _ in range(copies)]
-    vcs = [torch.randn(B, Hkv, L, D, device=dev, dtype=dt)
-           for _ in range(copies)]
+    kcs = _caches((B, Hkv, L, D), copies, fp8)
+    vcs = _caches((B, Hkv, L, D), copies, fp8)
     q = torch.randn(B, H, D, device=dev, dtype=dt)
     lens = torch.full((B,), L, device=dev, dtype=torch.int32)
     n_split, chunk = ops.decode_attention_splits(B * Hkv, L)
@@ -102,14 +126,15 @@ def bench_decode_kernel(B, L, H=32, Hkv=8, D=64, calls=400,
     for mode, n in (("hot", 1), ("rotating", copies)):
         def loop(count):
             for i in range(count):
-                ops.decode_attention(q, kcs[i % n], vcs[i % n], lens)
+                kc, vc, sc = _scales(kcs[i % n], vcs[i % n])
+                ops.decode_attention(q, kc, vc, lens, **sc)
         loop(max(20, n))                             # warm-up
         torch.cuda.synchronize()
         sec, _ = event_seconds(lambda: loop(calls))
         out[mode] = sec / calls
     print(json.dumps({
-        "bench": "attn_decode+combine", "B": B, "L": L, "H": H, "Hkv": Hkv,
-        "D": D, "n_split": n_split, "chunk": chunk,
+        "bench": "attn_decode+combine", "kv_dtype": "fp8" if fp8 else "bf16",
+        "B": B, "L": L, "H": H, "Hkv": Hkv, "D": D, "n_split": n_split, "chunk": chunk,
         "cache_bytes": cache_bytes, "copies": copies,
         "us_hot": out["hot"] * 1e6, "us_rotating": out["rotating"] * 1e6,
         "GBps_hot": cache_bytes / out["hot"] / 1e9,
@@ -117,15 +142,13 @@ def bench_decode_kernel(B, L, H=32, Hkv=8, D=64, calls=400,
 
 
 def bench_extend_kernel(B, T, L0, H=32, Hkv=8, D=64, calls=200,
-                        rotate_bytes=1 << 30):
+                        rotate_bytes=1 << 30, fp8=False):
     dev, dt = "cuda", torch.bfloat16
     Smax = L0 + T
-    cache_bytes = 2 * B * Hkv * Smax * D * 2         # K and V, bf16
+    cache_bytes = 2 * B * Hkv * Smax * (D + 4 if fp8 else D * 2)
     copies = max(1, min(512, -(-rotate_bytes // cache_bytes)))
-    kcs = [torch.randn(B, Hkv, Smax, D, device=dev, dtype=dt)
-           for _ in range(copies)]
-    vcs = [torch.randn(B, Hkv, Smax, D, device=dev, dtype=dt)
-           for _ in range(copies)]
+    kcs = _caches((B, Hkv, Smax, D), copies, fp8)
+    vcs = _caches((B, Hkv, Smax, D), copies, fp8)
     q = torch.randn(B, T, H, D, device=dev, dtype=dt)
     lens = torch.full((B,), L0, device=dev, dtype=torch.int32)
     lens_t = [lens + t + 1 for t in range(T)]
@@ -133,14 +156,17 @@ def bench_extend_kernel(B, T, L0, H=32, Hkv=8, D=64, calls=200,
         B * Hkv, T * (H // Hkv), Smax)
 
     def extend(kc, vc):
-        ops.extend_attention(q, kc, vc, lens)
+        kc, vc, sc = _scales(kc, vc)
+        ops.extend_attention(q, kc, vc, lens, **sc)
 
     def decodes(kc, vc):
+        kc, vc, sc = _scales(kc, vc)
         for t in range(T):
-            ops.decode_attention(q[:, t], kc, vc, lens_t[t])
+            ops.decode_attention(q[:, t], kc, vc, lens_t[t], **sc)
 
     def reference(kc, vc):
-        ops.torch_ref.extend_attention(q, kc, vc, lens)
+        kc, vc, sc = _scales(kc, vc)
+        ops.torch_ref.extend_attention(q, kc, vc, lens, **sc)
 
     base_name, base = (("decode_x_T", decodes) if T <= 8
                        else ("fp32_reference", reference))
@@ -156,8 +182,8 @@ def bench_extend_kernel(B, T, L0, H=32, Hkv=8, D=64, calls=200,
             sec, _ = event_seconds(lambda: loop(count))
             out[name + "_" + mode] = sec / count * 1e6
     print(json.dumps({
-        "bench": "attn_extend", "B": B, "T": T, "L0": L0, "H": H, "Hkv": Hkv,
-        "D": D, "n_blk": n_blk, "n_split": n_split, "chunk": chunk,
+        "bench": "attn_extend", "kv_dtype": "fp8" if fp8 else "bf16", "B": B,
+        "T": T, "L0": L0, "H": H, "Hkv": Hkv, "D": D, "n_blk": n_blk, "n_split": n_split, "chunk": chunk,
         "cache_bytes": cache_bytes, "copies": copies, "baseline": base_name,
         **{"us_" + k: v for k, v in out.items()}}), flush=True)
 
@@ -181,9 +207,11 @@ def main(argv=None):
     if not args.skip_kernel:
         for B in (1, 8):
             for L in (1024, 4096):
-                bench_decode_kernel(B, L)
+                for fp8 in (False, True):
+                    bench_decode_kernel(B, L, fp8=fp8)
         for B, T, L0 in ((1, 8, 1024), (8, 8, 4096), (1, 256, 3840)):
-            bench_extend_kernel(B, T, L0)
+            for fp8 in (False, True):
+                bench_extend_kernel(B, T, L0, fp8=fp8)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,9 @@ the host every token. --device-sampling (implies --kv-cache) runs
 acco_amd.models.generate instead: top-k / top-p and the draw happen on the
 model's device from a counter-based generator, so the same --seed gives other
 tokens than the CPU paths. --prefill-chunk N (implies --kv-cache) pushes the
-prompt through the cache N tokens at a time. Beyond the reference's surface (it has no
+prompt through the cache N tokens at a time. --kv-dtype fp8 (implies
+--kv-cache) stores the cache as e4m3 codes with one scale per row, about half
+the bytes per cached token. Beyond the reference's surface (it has no
 generation path); useful for judging what a checkpoint learned.
 
 Usage (config overrides use the same syntax as main.py):
@@ -44,12 +46,12 @@ def _sample(step: torch.Tensor, temperature: float,
 def generate(model, ids: torch.Tensor, max_new: int, temperature: float,
              max_len: int, seed: int = 0,
              use_cache: bool = False,
-             prefill_chunk: int = 0) -> torch.Tensor:
+             prefill_chunk: int = 0, kv_dtype=None) -> torch.Tensor:
     gen = torch.Generator(device="cpu").manual_seed(seed)
     model.eval()
-    if use_cache or prefill_chunk > 0:
+    if use_cache or prefill_chunk > 0 or kv_dtype is not None:
         return _generate_cached(model, ids, max_new, temperature, max_len,
-                                gen, prefill_chunk)
+                                gen, prefill_chunk, kv_dtype)
     for _ in range(max_new):
         out = model(ids[:, -max_len:])
         logits = out[0] if isinstance(out, tuple) else out
@@ -59,7 +61,7 @@ def generate(model, ids: torch.Tensor, max_new: int, temperature: float,
 
 
 def _generate_cached(model, ids, max_new, temperature, max_len, gen,
-                     prefill_chunk=0):
+                     prefill_chunk=0, kv_dtype=None):
     """One prefill (in slices of `prefill_chunk` tokens when that is set),
     then one decode_step per token; there is no sliding window over the
     context here, so it all has to fit."""
@@ -72,7 +74,7 @@ def _generate_cached(model, ids, max_new, temperature, max_len, gen,
             "slides over the context instead)")
     if max_new <= 0:
         return ids
-    cache = KVCache.allocate(model, ids.shape[0], total)
+    cache = KVCache.allocate(model, ids.shape[0], total, dtype=kv_dtype)
     if 0 < prefill_chunk < ids.shape[1]:
         logits = prefill_chunked(model, ids, None, cache, prefill_chunk)
     else:
@@ -103,6 +105,10 @@ def main(argv=None) -> str:
                     help="push the prompt through the cache this many "
                          "tokens at a time (implies --kv-cache; 0 = one "
                          "prefill of the whole prompt)")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: keep the KV cache as e4m3 codes with one "
+                         "scale per row (implies --kv-cache); bf16: in the "
+                         "model's dtype")
     ap.add_argument("--device-sampling", action="store_true",
                     help="sample on the model's device with "
                          "acco_amd.models.generate (implies --kv-cache): no "
@@ -137,6 +143,7 @@ def main(argv=None) -> str:
     model = model.to(device)
 
     ids = torch.tensor([tok.encode(args.prompt).ids], device=device)
+    kv_dtype = torch.float8_e4m3fn if args.kv_dtype == "fp8" else None
     max_len = int(model.cfg.max_position_embeddings)
     if args.device_sampling:
         from acco_amd.models import generate as generate_on_device
@@ -146,12 +153,12 @@ def main(argv=None) -> str:
             model, ids, max_new=max(args.max_new, 0),
             temperature=max(args.temperature, 0.0), top_k=args.top_k,
             top_p=args.top_p, seed=args.seed,
-            prefill_chunk=args.prefill_chunk)
+            prefill_chunk=args.prefill_chunk, kv_dtype=kv_dtype)
         out = out[:, :ids.shape[1] + int(n_new[0])]
     else:
         out = generate(model, ids, args.max_new, args.temperature, max_len,
                        seed=args.seed, use_cache=args.kv_cache,
-                       prefill_chunk=args.prefill_chunk)
+                       prefill_chunk=args.prefill_chunk, kv_dtype=kv_dtype)
     text = tok.decode(out[0].tolist())
     print(text)
     return text
