@@ -22,7 +22,8 @@ def generate(model, input_ids: torch.Tensor,
              temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
              seed: int = 0, eos_token_id: Optional[int] = None,
              prefill_chunk: int = 0,
-             kv_dtype: Optional[torch.dtype] = None
+             kv_dtype: Optional[torch.dtype] = None,
+             weight_dtype: Optional[torch.dtype] = None
              ) -> Tuple[torch.Tensor, torch.Tensor]:
     """(tokens int64 [B, S + max_new], n_generated int64 [B]) for prompts
     `input_ids` [B, S] of `model` (LlamaForCausalLM or GPTNeoForCausalLM, in
@@ -41,9 +42,22 @@ def generate(model, input_ids: torch.Tensor,
     the prefill's activation memory; 0 = one prefill of the whole prompt.
     kv_dtype: the dtype of the KV cache (KVCache.allocate; None = the
     model's); torch.float8_e4m3fn stores it quantised, about half the bytes
-    per cached token."""
+    per cached token.
+    weight_dtype: None = the model's own linears; torch.float8_e4m3fn
+    generates from quant.quantize_weights(model) (e4m3 weight codes with one
+    scale per output row, ops.linear_w8), about half the weight bytes per
+    token; the copy is made per call, so quantise once and pass the result
+    when generating more than once (a model that already holds W8Linears is
+    used as it is)."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B, S], got {input_ids.shape}")
+    if weight_dtype is not None:
+        from acco_amd.models.quant import has_w8_linears, quantize_weights
+        if weight_dtype != torch.float8_e4m3fn:
+            raise ValueError("weight_dtype must be None or torch."
+                             f"float8_e4m3fn, got {weight_dtype}")
+        if not has_w8_linears(model):
+            model = quantize_weights(model)
     B, S = input_ids.shape
     max_new = int(max_new)
     if max_new < 0:

@@ -376,6 +376,53 @@ def extend_attention_splits(bhkv: int, cols: int,
     return int(n_blk), int(n_split), int(chunk)
 
 
+W8_MAX_ROWS = 64      # the most rows of x the linear_w8 kernel takes
+
+
+def linear_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [..., N] = (x [..., K] @ float(codes)^T) * scale (+ bias) for a
+    weight stored as e4m3 codes [N, K] with one fp32 scale per output row
+    (torch_ref.weight_quantize; torch_ref.linear_w8 has the semantics). The
+    leading dims of x flatten to M rows.
+
+    On the GPU, bf16 x, e4m3 codes and K % 64 == 0 with M <= 64 (decode_step,
+    a short extend) run the HIP kernel: half the weight bytes of a bf16
+    linear, exact products, fp32 accumulation, one rounding to bf16. x may be
+    a strided view with a contiguous last dim. With M > 64 (prefill, a long
+    extend) the product is torch.matmul on a temporary bf16 copy of the codes
+    (exact: every e4m3 value is a bf16), scaled and biased in fp32: one more
+    bf16 rounding than the kernel, on the unscaled product, and N·K bf16
+    elements of scratch per call. CPU tensors, other dtypes, other K and
+    ACCO_FORCE_REF=1 run the torch reference."""
+    K, N = x.shape[-1], codes.shape[0]
+    if (_use_ref(x) or x.dtype != torch.bfloat16
+            or codes.dtype != FP8 or K % 64 != 0 or K == 0):
+        return torch_ref.linear_w8(x, codes, scale, bias)
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    if M == 0:
+        return x.new_empty(*x.shape[:-1], N)
+    if M > W8_MAX_ROWS:
+        y = torch.matmul(x2, codes.to(x.dtype).t()).float() * scale
+        if bias is not None:
+            y = y + bias.float()
+        return y.to(x.dtype).view(*x.shape[:-1], N)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    y = hip_ext().linear_w8(x2, codes, scale, bias)
+    return y.view(*x.shape[:-1], N)
+
+
+def linear_w8_splits(m: int, n: int, k: int) -> Tuple[int, int]:
+    """(n_split, k_chunk) of the HIP linear_w8 for M rows of x, N output rows
+    and K columns: workgroup i of a block of weight rows owns the columns
+    [i·k_chunk, (i+1)·k_chunk). A host function of its three arguments
+    only."""
+    n_split, k_chunk = hip_ext().linear_w8_grid(int(m), int(n), int(k))
+    return int(n_split), int(k_chunk)
+
+
 def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int, step: int,
                   done: Optional[torch.Tensor] = None, eos_id: int = -1

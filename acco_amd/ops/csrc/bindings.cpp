@@ -1328,6 +1328,70 @@ at::Tensor attn_extend_fp8(at::Tensor q, at::Tensor k_cache,
                          scale, window);
 }
 
+// ---- weight-only e4m3 linear for decode (linear_w8.hip)
+static void check_w8_sizes(int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(M >= 1 && M <= 64 && N >= 1 && N < (1LL << 24) && K >= 64 &&
+              K < (1LL << 24) && K % 64 == 0,
+              "linear_w8: need 1 <= M <= 64, 1 <= N < 2^24 and K < 2^24 a "
+              "positive multiple of 64, got M=", M, " N=", N, " K=", K);
+}
+
+// (n_split, k_chunk) of linear_w8 for its three sizes: split i owns the
+// columns [i*k_chunk, (i+1)*k_chunk) of x and of the codes
+std::vector<int64_t> linear_w8_grid(int64_t M, int64_t N, int64_t K) {
+  check_w8_sizes(M, N, K);
+  int n_split, k_chunk;
+  acco_linear_w8_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
+  return {n_split, k_chunk};
+}
+
+// y [M, N] bf16 = x . codes^T * scale (+ bias). The argument contract: x CUDA
+// bf16 [M, K] with a contiguous last dim, rows stride(0) >= K apart (a
+// multiple of 8) on a 16-byte aligned base; codes contiguous float8_e4m3fn
+// [N, K], 16-byte aligned; scale contiguous fp32 [N]; bias, when given,
+// contiguous bf16 [N]; all on x's device; sizes as check_w8_sizes.
+at::Tensor linear_w8(at::Tensor x, at::Tensor codes, at::Tensor scale,
+                     c10::optional<at::Tensor> bias) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
+              "x must be CUDA bf16 [M, K], got ", x.scalar_type(), " ",
+              x.sizes(), " on ", x.device());
+  TORCH_CHECK(codes.is_cuda() && codes.device() == x.device() &&
+              codes.scalar_type() == at::kFloat8_e4m3fn &&
+              codes.is_contiguous() && codes.dim() == 2 &&
+              codes.size(1) == x.size(1),
+              "codes must be contiguous float8_e4m3fn [N, K = ", x.size(1),
+              "] on ", x.device(), ", got ", codes.scalar_type(), " ",
+              codes.sizes(), " on ", codes.device());
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  check_w8_sizes(M, N, K);
+  const int64_t rs = M > 1 ? x.stride(0) : K;
+  TORCH_CHECK(x.stride(1) == 1 && rs >= K && rs % 8 == 0,
+              "x must have a contiguous last dim and rows a multiple of 8 "
+              "elements, at least K, apart, got strides ", x.strides());
+  TORCH_CHECK(aligned_to(x, 16) && aligned_to(codes, 16),
+              "x and codes must be 16-byte aligned");
+  check_f32_vec(scale, N, x, "scale");
+  TORCH_CHECK(scale.dim() == 1, "scale must be [N], got ", scale.sizes());
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                bias->scalar_type() == at::kBFloat16 &&
+                bias->is_contiguous() && bias->dim() == 1 &&
+                bias->size(0) == N, "bias must be contiguous bf16 [N] = [", N,
+                "] on ", x.device(), ", got ", bias->scalar_type(), " ",
+                bias->sizes(), " on ", bias->device());
+  int n_split, k_chunk;
+  acco_linear_w8_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
+  auto y = at::empty({M, N}, x.options());
+  auto ws = at::empty({n_split > 1 ? n_split * M * N : 0},
+                      x.options().dtype(at::kFloat));
+  acco_linear_w8(x.data_ptr(), codes.data_ptr(), scale.data_ptr<float>(),
+                 bias.has_value() ? bias->data_ptr() : nullptr, y.data_ptr(),
+                 ws.data_ptr<float>(), (int)M, (int)N, (int)K, rs,
+                 cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return y;
+}
+
 // ---- on-device sampling (sample.hip)
 // (token int64 [B], logprob fp32 [B], thr bf16 [B], n_kept int32 [B]) of one
 // draw per row. The argument contract: logits CUDA bf16 [B, V] whose last dim
@@ -1423,6 +1487,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("cache_len"), py::arg("scale"),
         py::arg("window"));
+  m.def("linear_w8_grid", &linear_w8_grid, py::arg("M"), py::arg("N"),
+        py::arg("K"));
+  m.def("linear_w8", &linear_w8, py::arg("x"), py::arg("codes"),
+        py::arg("scale"), py::arg("bias"));
   m.def("fused_adamw", &fused_adamw,
         "Fused sharded AdamW (gfx950): cast+scale+AdamW+bf16 writeout; "
         "commit=false = ACCO tentative step");

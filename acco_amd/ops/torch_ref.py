@@ -187,6 +187,26 @@ def kv_dequantize(codes: torch.Tensor, scale: torch.Tensor,
     return codes.to(dtype) * scale.to(dtype)[..., None]
 
 
+def weight_quantize(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(codes e4m3 [N, K], scale fp32 [N]) of a linear's weight [N, K]: the
+    format of the e4m3 KV cache applied to the rows of `w` (kv_quantize), one
+    scale per output row. The scale of a row is a factor of its whole dot
+    product, so it multiplies the finished sum and never enters the K loop."""
+    return kv_quantize(w)
+
+
+def linear_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [..., N] = (x [..., K] @ float(codes [N, K])^T) * scale [N] (+ bias
+    [N]) for weights stored by weight_quantize, computed in fp32 (fp64 for an
+    fp64 x) and returned in x's dtype."""
+    acc = torch.promote_types(x.dtype, torch.float32)
+    y = (x.to(acc) @ codes.to(acc).t()) * scale.to(acc)
+    if bias is not None:
+        y = y + bias.to(acc)
+    return y.to(x.dtype)
+
+
 @torch.no_grad()
 def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
               cache_len: torch.Tensor, k: torch.Tensor, v: torch.Tensor,

@@ -12,7 +12,10 @@ model's device from a counter-based generator, so the same --seed gives other
 tokens than the CPU paths. --prefill-chunk N (implies --kv-cache) pushes the
 prompt through the cache N tokens at a time. --kv-dtype fp8 (implies
 --kv-cache) stores the cache as e4m3 codes with one scale per row, about half
-the bytes per cached token. Beyond the reference's surface (it has no
+the bytes per cached token. --weight-dtype fp8 generates from
+models.quantize_weights(model): every linear as e4m3 codes with one scale per
+output row, half the weight bytes per token (any of the paths above; the HIP
+kernel serves a bf16 model on the GPU). Beyond the reference's surface (it has no
 generation path); useful for judging what a checkpoint learned.
 
 Usage (config overrides use the same syntax as main.py):
@@ -109,6 +112,10 @@ def main(argv=None) -> str:
                     help="fp8: keep the KV cache as e4m3 codes with one "
                          "scale per row (implies --kv-cache); bf16: in the "
                          "model's dtype")
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: generate from a copy of the model whose "
+                         "linears hold e4m3 weight codes with one scale per "
+                         "output row; bf16: the checkpoint's own weights")
     ap.add_argument("--device-sampling", action="store_true",
                     help="sample on the model's device with "
                          "acco_amd.models.generate (implies --kv-cache): no "
@@ -141,6 +148,9 @@ def main(argv=None) -> str:
                         vocab_size_override=tok.get_vocab_size())
     load_pretrained(model, args.ckpt)
     model = model.to(device)
+    if args.weight_dtype == "fp8":
+        from acco_amd.models import quantize_weights
+        model = quantize_weights(model.eval())
 
     ids = torch.tensor([tok.encode(args.prompt).ids], device=device)
     kv_dtype = torch.float8_e4m3fn if args.kv_dtype == "fp8" else None
