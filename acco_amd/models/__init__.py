@@ -9,11 +9,11 @@ from acco_amd.models.config import GPTNeoConfig, LlamaConfig
 from acco_amd.models.generation import generate
 from acco_amd.models.gptneo import GPTNeoForCausalLM
 from acco_amd.models.llama import LlamaForCausalLM
-from acco_amd.models.quant import W8Linear, quantize_weights
+from acco_amd.models.quant import W4Linear, W8Linear, quantize_weights
 
 __all__ = ["build_model", "load_pretrained", "generate", "GPTNeoConfig",
            "LlamaConfig", "GPTNeoForCausalLM", "LlamaForCausalLM",
-           "W8Linear", "quantize_weights"]
+           "W4Linear", "W8Linear", "quantize_weights"]
 
 
 def build_model(model_cfg, vocab_size_override=None):

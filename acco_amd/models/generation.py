@@ -48,16 +48,21 @@ def generate(model, input_ids: torch.Tensor,
     scale per output row, ops.linear_w8), about half the weight bytes per
     token; the copy is made per call, so quantise once and pass the result
     when generating more than once (a model that already holds W8Linears is
-    used as it is)."""
+    used as it is). torch.float4_e2m1fn_x2 does the same in OCP MXFP4
+    (quantize_weights(model, dtype), ops.linear_w4): e2m1 codes with one
+    power-of-two scale per 32 weights, about 0.53 bytes per weight; a model
+    that already holds quantised linears of either kind is used as it is."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B, S], got {input_ids.shape}")
     if weight_dtype is not None:
-        from acco_amd.models.quant import has_w8_linears, quantize_weights
-        if weight_dtype != torch.float8_e4m3fn:
-            raise ValueError("weight_dtype must be None or torch."
-                             f"float8_e4m3fn, got {weight_dtype}")
-        if not has_w8_linears(model):
-            model = quantize_weights(model)
+        from acco_amd.models.quant import (has_quantized_linears,
+                                           quantize_weights)
+        if weight_dtype not in (torch.float8_e4m3fn,
+                                torch.float4_e2m1fn_x2):
+            raise ValueError("weight_dtype must be None, torch.float8_e4m3fn "
+                             f"or torch.float4_e2m1fn_x2, got {weight_dtype}")
+        if not has_quantized_linears(model):
+            model = quantize_weights(model, weight_dtype)
     B, S = input_ids.shape
     max_new = int(max_new)
     if max_new < 0:

@@ -2,7 +2,11 @@
 stored as one-byte codes with one fp32 scale per output row
 (torch_ref.weight_quantize), half the weight bytes a decode step streams and
 half the weight memory of a model that is only generated from. Activations
-stay bf16; `ops.linear_w8` is the product. Nothing here trains."""
+stay bf16; `ops.linear_w8` is the product. Nothing here trains.
+
+The same in OCP MXFP4 (`W4Linear`, `ops.linear_w4`): e2m1 codes with one
+power-of-two scale per 32 weights (torch_ref.weight_quantize_mxfp4), about
+0.53 bytes per weight."""
 
 from __future__ import annotations
 
@@ -51,16 +55,60 @@ class W8Linear(nn.Module):
                 f"{self.out_features}, bias={self.bias is not None}")
 
 
-def _copy_module(mod: nn.Module) -> nn.Module:
-    """A new module tree over the same tensors: nn.Linear -> W8Linear, every
-    other module a shallow copy with its own parameter / buffer / child
-    tables, so embeddings and norm weights are shared with the original."""
+class W4Linear(nn.Module):
+    """A linear whose weight is MXFP4: uint8 `codes` [out, in / 2] and uint8
+    `scales` [out, in / 32] (buffers, as is the optional `bias`): forward is
+    ops.linear_w4. in_features must be a multiple of 32."""
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor,
+                 bias: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.out_features, self.in_features = codes.shape[0], 2 * codes.shape[1]
+        self.register_buffer("codes", codes)
+        self.register_buffer("scales", scales)
+        self.register_buffer("bias", bias)
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear) -> "W4Linear":
+        codes, scales = ops.torch_ref.weight_quantize_mxfp4(lin.weight.detach())
+        bias = None if lin.bias is None else lin.bias.detach()
+        return cls(codes, scales, bias)
+
+    def _apply(self, fn, recurse=True):
+        """Moves and casts as any module, but the weight keeps its format: a
+        dtype cast of the model reaches the bias only. The buffers are
+        integers, which a floating-point cast leaves alone; an explicit cast
+        to another integer type is undone here."""
+        super()._apply(fn, recurse)
+        self.codes = self.codes.to(torch.uint8)
+        self.scales = self.scales.to(torch.uint8)
+        return self
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.linear_w4(x, self.codes, self.scales, self.bias)
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features="
+                f"{self.out_features}, bias={self.bias is not None}")
+
+
+FP4 = torch.float4_e2m1fn_x2
+
+
+def _copy_module(mod: nn.Module, dtype: torch.dtype) -> nn.Module:
+    """A new module tree over the same tensors: nn.Linear -> W8Linear (or
+    W4Linear), every other module a shallow copy with its own parameter /
+    buffer / child tables, so embeddings and norm weights are shared with the
+    original."""
     if isinstance(mod, nn.Linear):
-        return W8Linear.from_linear(mod)
+        if dtype != FP4:
+            return W8Linear.from_linear(mod)
+        # MXFP4 blocks are 32 wide: a linear they do not tile stays as it is
+        return W4Linear.from_linear(mod) if mod.in_features % 32 == 0 else mod
     new = copy.copy(mod)
     new._parameters = dict(mod._parameters)
     new._buffers = dict(mod._buffers)
-    new._modules = {name: None if child is None else _copy_module(child)
+    new._modules = {name: None if child is None else _copy_module(child, dtype)
                     for name, child in mod._modules.items()}
     for attr in _FUSE_ATTRS:
         # arena views of the bf16 weights: the copy takes the per-projection
@@ -71,18 +119,25 @@ def _copy_module(mod: nn.Module) -> nn.Module:
 
 
 @torch.no_grad()
-def quantize_weights(model: nn.Module) -> nn.Module:
+def quantize_weights(model: nn.Module,
+                     dtype: torch.dtype = torch.float8_e4m3fn) -> nn.Module:
     """A copy of `model` (LlamaForCausalLM or GPTNeoForCausalLM, in eval mode)
     for generation whose every nn.Linear is a W8Linear of the same weight; a
     tied lm_head gets codes of its own and the embedding stays as it is.
     Embeddings and norm weights are the original's tensors, not copies.
     prefill, decode_step, extend and forward work on the result unchanged;
-    the original is not modified."""
+    the original is not modified.
+    dtype: torch.float8_e4m3fn (W8Linear) or torch.float4_e2m1fn_x2: MXFP4
+    W4Linears, except that a linear whose in_features is not a multiple of 32
+    stays the original's bf16 nn.Linear in the copy."""
     if model.training:
         raise ValueError("quantize_weights is for generation: call "
                          "model.eval() first")
-    return _copy_module(model).eval()
+    if dtype not in (torch.float8_e4m3fn, FP4):
+        raise ValueError("quantize_weights: dtype must be torch.float8_e4m3fn "
+                         f"or torch.float4_e2m1fn_x2, got {dtype}")
+    return _copy_module(model, dtype).eval()
 
 
-def has_w8_linears(model: nn.Module) -> bool:
-    return any(isinstance(m, W8Linear) for m in model.modules())
+def has_quantized_linears(model: nn.Module) -> bool:
+    return any(isinstance(m, (W8Linear, W4Linear)) for m in model.modules())

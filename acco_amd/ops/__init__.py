@@ -423,6 +423,55 @@ def linear_w8_splits(m: int, n: int, k: int) -> Tuple[int, int]:
     return int(n_split), int(k_chunk)
 
 
+W4_MAX_ROWS = 64      # the most rows of x the linear_w4 kernel takes
+
+
+def linear_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [..., N] = x [..., K] @ dequant(codes, scales)^T (+ bias) for a
+    weight stored in OCP MXFP4: uint8 codes [N, K / 2] of two e2m1 values
+    each and uint8 e8m0 scales [N, K / 32], one per 32 k
+    (torch_ref.weight_quantize_mxfp4; torch_ref.linear_w4 has the semantics).
+    The leading dims of x flatten to M rows.
+
+    On the GPU, bf16 x and K % 128 == 0 with M <= 64 (decode_step, a short
+    extend) run the HIP kernel: about 0.53 bytes per weight, the exact weight
+    as the bf16 MFMA operand (the hardware convert applies the block scale),
+    fp32 accumulation, one rounding to bf16. x may be a strided view with a
+    contiguous last dim. With M > 64 (prefill, a long extend) the product is
+    torch.matmul on a temporary bf16 dequantisation (exact), the bias added
+    in fp32: one more bf16 rounding than the kernel and N·K bf16 elements of
+    scratch per call. CPU tensors, other dtypes, other K and ACCO_FORCE_REF=1
+    run the torch reference."""
+    K, N = x.shape[-1], codes.shape[0]
+    if (_use_ref(x) or x.dtype != torch.bfloat16
+            or codes.dtype != torch.uint8 or K % 128 != 0 or K == 0):
+        return torch_ref.linear_w4(x, codes, scales, bias)
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    if M == 0:
+        return x.new_empty(*x.shape[:-1], N)
+    if M > W4_MAX_ROWS:
+        w = torch_ref.weight_dequantize_mxfp4(codes, scales, x.dtype)
+        y = torch.matmul(x2, w.t())
+        if bias is not None:
+            y = (y.float() + bias.float()).to(x.dtype)
+        return y.view(*x.shape[:-1], N)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    y = hip_ext().linear_w4(x2, codes, scales, bias)
+    return y.view(*x.shape[:-1], N)
+
+
+def linear_w4_splits(m: int, n: int, k: int) -> Tuple[int, int]:
+    """(n_split, k_chunk) of the HIP linear_w4 for M rows of x, N output rows
+    and K columns: workgroup i of a block of weight rows owns the columns
+    [i·k_chunk, (i+1)·k_chunk). A host function of its three arguments
+    only."""
+    n_split, k_chunk = hip_ext().linear_w4_grid(int(m), int(n), int(k))
+    return int(n_split), int(k_chunk)
+
+
 def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int, step: int,
                   done: Optional[torch.Tensor] = None, eos_id: int = -1

@@ -1392,6 +1392,77 @@ at::Tensor linear_w8(at::Tensor x, at::Tensor codes, at::Tensor scale,
   return y;
 }
 
+// ---- weight-only MXFP4 linear for decode (linear_w4.hip)
+static void check_w4_sizes(int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(M >= 1 && M <= 64 && N >= 1 && N < (1LL << 24) && K >= 128 &&
+              K < (1LL << 24) && K % 128 == 0,
+              "linear_w4: need 1 <= M <= 64, 1 <= N < 2^24 and K < 2^24 a "
+              "positive multiple of 128, got M=", M, " N=", N, " K=", K);
+}
+
+// (n_split, k_chunk) of linear_w4 for its three sizes: split i owns the
+// columns [i*k_chunk, (i+1)*k_chunk) of x and of the weight
+std::vector<int64_t> linear_w4_grid(int64_t M, int64_t N, int64_t K) {
+  check_w4_sizes(M, N, K);
+  int n_split, k_chunk;
+  acco_linear_w4_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
+  return {n_split, k_chunk};
+}
+
+// y [M, N] bf16 = x . dequant(codes, scales)^T (+ bias). The argument
+// contract: x CUDA bf16 [M, K] with a contiguous last dim, rows stride(0) >= K
+// apart (a multiple of 8) on a 16-byte aligned base; codes contiguous uint8
+// [N, K / 2] (two e2m1 per byte), 16-byte aligned; scales contiguous uint8
+// [N, K / 32] (e8m0), 4-byte aligned; bias, when given, contiguous bf16 [N];
+// all on x's device; sizes as check_w4_sizes.
+at::Tensor linear_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
+                     c10::optional<at::Tensor> bias) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
+              "x must be CUDA bf16 [M, K], got ", x.scalar_type(), " ",
+              x.sizes(), " on ", x.device());
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(codes.is_cuda() && codes.device() == x.device() &&
+              codes.scalar_type() == at::kByte && codes.is_contiguous() &&
+              codes.dim() == 2 && codes.size(1) * 2 == K,
+              "codes must be contiguous uint8 [N, K / 2 = ", K / 2, "] on ",
+              x.device(), ", got ", codes.scalar_type(), " ", codes.sizes(),
+              " on ", codes.device());
+  const int64_t N = codes.size(0);
+  check_w4_sizes(M, N, K);
+  TORCH_CHECK(scales.is_cuda() && scales.device() == x.device() &&
+              scales.scalar_type() == at::kByte && scales.is_contiguous() &&
+              scales.dim() == 2 && scales.size(0) == N &&
+              scales.size(1) * 32 == K,
+              "scales must be contiguous uint8 [N, K / 32] = [", N, ", ",
+              K / 32, "] on ", x.device(), ", got ", scales.scalar_type(), " ",
+              scales.sizes(), " on ", scales.device());
+  const int64_t rs = M > 1 ? x.stride(0) : K;
+  TORCH_CHECK(x.stride(1) == 1 && rs >= K && rs % 8 == 0,
+              "x must have a contiguous last dim and rows a multiple of 8 "
+              "elements, at least K, apart, got strides ", x.strides());
+  TORCH_CHECK(aligned_to(x, 16) && aligned_to(codes, 16) &&
+              aligned_to(scales, 4),
+              "x and codes must be 16-byte aligned, scales 4-byte aligned");
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                bias->scalar_type() == at::kBFloat16 &&
+                bias->is_contiguous() && bias->dim() == 1 &&
+                bias->size(0) == N, "bias must be contiguous bf16 [N] = [", N,
+                "] on ", x.device(), ", got ", bias->scalar_type(), " ",
+                bias->sizes(), " on ", bias->device());
+  int n_split, k_chunk;
+  acco_linear_w4_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
+  auto y = at::empty({M, N}, x.options());
+  auto ws = at::empty({n_split > 1 ? n_split * M * N : 0},
+                      x.options().dtype(at::kFloat));
+  acco_linear_w4(x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+                 bias.has_value() ? bias->data_ptr() : nullptr, y.data_ptr(),
+                 ws.data_ptr<float>(), (int)M, (int)N, (int)K, rs,
+                 cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return y;
+}
+
 // ---- on-device sampling (sample.hip)
 // (token int64 [B], logprob fp32 [B], thr bf16 [B], n_kept int32 [B]) of one
 // draw per row. The argument contract: logits CUDA bf16 [B, V] whose last dim
@@ -1491,6 +1562,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("K"));
   m.def("linear_w8", &linear_w8, py::arg("x"), py::arg("codes"),
         py::arg("scale"), py::arg("bias"));
+  m.def("linear_w4_grid", &linear_w4_grid, py::arg("M"), py::arg("N"),
+        py::arg("K"));
+  m.def("linear_w4", &linear_w4, py::arg("x"), py::arg("codes"),
+        py::arg("scales"), py::arg("bias"));
   m.def("fused_adamw", &fused_adamw,
         "Fused sharded AdamW (gfx950): cast+scale+AdamW+bf16 writeout; "
         "commit=false = ACCO tentative step");

@@ -156,6 +156,19 @@ void acco_linear_w8(const void* x, const void* codes, const float* scale,
                     const void* bias, void* y, float* workspace, int M, int N,
                     int K, long long x_rs, hipStream_t stream);
 
+// ---- linear_w4.hip
+// Weight-only MXFP4 linear for a few rows: y [M, N] bf16 contiguous = x [M, K]
+// bf16 (rows x_rs apart) . dequant(codes [N, K / 2] bytes of two e2m1 each,
+// scales [N, K / 32] e8m0 bytes, both contiguous)^T (+ bias [N] bf16,
+// nullable). 1 <= M <= 64, K % 128 == 0, 1 <= N, K < 2^24. K is split over
+// n_split workgroups of k_chunk columns each (host only, a function of the
+// three sizes); workspace: n_split * M * N fp32 when n_split > 1 (written
+// before it is read), unused otherwise.
+void acco_linear_w4_grid(int M, int N, int K, int* n_split, int* k_chunk);
+void acco_linear_w4(const void* x, const void* codes, const void* scales,
+                    const void* bias, void* y, float* workspace, int M, int N,
+                    int K, long long x_rs, hipStream_t stream);
+
 // ---- ce.hip
 // bf16 logits on a 16-byte aligned base (any V). A token is valid iff
 // 0 <= target < V; any other target (-100, >= V) is ignored: lse 0, no loss,

@@ -207,6 +207,73 @@ def linear_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
     return y.to(x.dtype)
 
 
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)     # magnitude of code & 7
+
+
+def weight_quantize_mxfp4(w: torch.Tensor
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(codes uint8 [N, K / 2], scales uint8 [N, K / 32]) of a linear's weight
+    [N, K] in OCP MXFP4; K must be a multiple of 32. A code is a nibble: sign,
+    two exponent bits, one mantissa bit, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4,
+    6; byte i of a row holds k = 2 i in its low nibble and k = 2 i + 1 in its
+    high nibble (the packing of torch.float4_e2m1fn_x2, stored as plain
+    uint8). Every 32 consecutive k share one e8m0 scale byte s, the scale
+    2^(s - 127).
+
+    The exponent is the OCP MX rule in exact operations: with amax the
+    block's largest |w| in fp32, e = floor(log2(amax)) - 2 (torch.frexp),
+    clamped into [-120, 120] so that every dequantised value is a normal bf16
+    and s << 23 is the scale as fp32 bits; s = e + 127. A zero block takes
+    byte 127 and zero codes; byte 255 (NaN) is never produced. A code is
+    w / 2^e rounded to the nearest magnitude, ties to the even code,
+    saturating at +-6: amax / 2^e lies in [4, 8), so values in (6, 8) * 2^e
+    clip to 6 * 2^e. That is the specification's behaviour, not an
+    oversight."""
+    N, K = w.shape
+    if K % 32 != 0:
+        raise ValueError(f"weight_quantize_mxfp4 needs K % 32 == 0, got {K}")
+    blocks = w.detach().float().reshape(N, K // 32, 32)
+    amax = blocks.abs().amax(dim=-1)
+    e = torch.frexp(amax)[1] - 3      # amax = m * 2^exp, m in [0.5, 1)
+    e = torch.where(amax > 0, e.clamp(-120, 120), torch.zeros_like(e))
+    v = torch.ldexp(blocks.double(), -e[..., None]).abs()    # exact
+    grid = torch.tensor(_E2M1, dtype=torch.float64, device=w.device)
+    hi = torch.bucketize(v, grid).clamp(max=7)      # first magnitude >= v
+    lo = (hi - 1).clamp(min=0)
+    d_lo, d_hi = v - grid[lo], grid[hi] - v
+    code = torch.where((d_lo < d_hi) | ((d_lo == d_hi) & (lo % 2 == 0)),
+                       lo, hi)
+    code = (code + 8 * (blocks < 0)).to(torch.uint8)
+    code = code.reshape(N, K // 2, 2)
+    return code[..., 0] | (code[..., 1] << 4), (e + 127).to(torch.uint8)
+
+
+def weight_dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor,
+                            dtype: torch.dtype) -> torch.Tensor:
+    """The [N, K] values of MXFP4 codes [N, K / 2] and scales [N, K / 32] in
+    `dtype`: exact in bf16 and anything wider (a two-bit significand times a
+    power of two), for the scale bytes weight_quantize_mxfp4 produces."""
+    N = codes.shape[0]
+    nib = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(N, -1, 32)
+    lut = torch.tensor(_E2M1 + tuple(-m for m in _E2M1), dtype=dtype,
+                       device=codes.device)
+    scale = torch.ldexp(torch.ones((), device=codes.device),
+                        scales.int() - 127).to(dtype)
+    return (lut[nib.int()] * scale[..., None]).reshape(N, -1)
+
+
+def linear_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [..., N] = x [..., K] @ dequant(codes, scales)^T (+ bias [N]) for
+    weights stored by weight_quantize_mxfp4, computed in fp32 (fp64 for an
+    fp64 x) and returned in x's dtype."""
+    acc = torch.promote_types(x.dtype, torch.float32)
+    y = x.to(acc) @ weight_dequantize_mxfp4(codes, scales, acc).t()
+    if bias is not None:
+        y = y + bias.to(acc)
+    return y.to(x.dtype)
+
+
 @torch.no_grad()
 def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
               cache_len: torch.Tensor, k: torch.Tensor, v: torch.Tensor,

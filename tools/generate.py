@@ -15,7 +15,9 @@ prompt through the cache N tokens at a time. --kv-dtype fp8 (implies
 the bytes per cached token. --weight-dtype fp8 generates from
 models.quantize_weights(model): every linear as e4m3 codes with one scale per
 output row, half the weight bytes per token (any of the paths above; the HIP
-kernel serves a bf16 model on the GPU). Beyond the reference's surface (it has no
+kernel serves a bf16 model on the GPU). --weight-dtype fp4 does the same in
+OCP MXFP4: e2m1 codes with one power-of-two scale per 32 weights, about 0.53
+bytes per weight. Beyond the reference's surface (it has no
 generation path); useful for judging what a checkpoint learned.
 
 Usage (config overrides use the same syntax as main.py):
@@ -112,10 +114,12 @@ def main(argv=None) -> str:
                     help="fp8: keep the KV cache as e4m3 codes with one "
                          "scale per row (implies --kv-cache); bf16: in the "
                          "model's dtype")
-    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8", "fp4"),
+                    default="bf16",
                     help="fp8: generate from a copy of the model whose "
                          "linears hold e4m3 weight codes with one scale per "
-                         "output row; bf16: the checkpoint's own weights")
+                         "output row; fp4: MXFP4 codes with one scale per 32 "
+                         "weights; bf16: the checkpoint's own weights")
     ap.add_argument("--device-sampling", action="store_true",
                     help="sample on the model's device with "
                          "acco_amd.models.generate (implies --kv-cache): no "
@@ -148,9 +152,11 @@ def main(argv=None) -> str:
                         vocab_size_override=tok.get_vocab_size())
     load_pretrained(model, args.ckpt)
     model = model.to(device)
-    if args.weight_dtype == "fp8":
+    if args.weight_dtype != "bf16":
         from acco_amd.models import quantize_weights
-        model = quantize_weights(model.eval())
+        model = quantize_weights(
+            model.eval(), torch.float8_e4m3fn if args.weight_dtype == "fp8"
+            else torch.float4_e2m1fn_x2)
 
     ids = torch.tensor([tok.encode(args.prompt).ids], device=device)
     kv_dtype = torch.float8_e4m3fn if args.kv_dtype == "fp8" else None
