@@ -20,76 +20,69 @@ from acco_amd import ops
 from acco_amd.models.fuse import _FUSE_ATTRS
 
 
-class W8Linear(nn.Module):
-    """A linear whose weight is e4m3 `codes` [out, in] and fp32 `scale` [out]
-    (buffers, as is the optional `bias`): forward is ops.linear_w8."""
+class _QuantLinear(nn.Module):
+    """What W8Linear and W4Linear share: the weight as two buffers, `codes`
+    and the one `_SCALE` names (as is the optional `bias`), pinned to the
+    dtypes `_DTYPES`. A subclass gives those, `_quantize` and `forward`."""
 
     def __init__(self, codes: torch.Tensor, scale: torch.Tensor,
                  bias: Optional[torch.Tensor] = None):
         super().__init__()
-        self.out_features, self.in_features = codes.shape
         self.register_buffer("codes", codes)
-        self.register_buffer("scale", scale)
+        self.register_buffer(self._SCALE, scale)
         self.register_buffer("bias", bias)
 
     @classmethod
-    def from_linear(cls, lin: nn.Linear) -> "W8Linear":
-        codes, scale = ops.torch_ref.weight_quantize(lin.weight.detach())
+    def from_linear(cls, lin: nn.Linear):
+        codes, scale = cls._quantize(lin.weight.detach())
         bias = None if lin.bias is None else lin.bias.detach()
         return cls(codes, scale, bias)
 
     def _apply(self, fn, recurse=True):
         """Moves and casts as any module, but the weight keeps its format: a
         dtype cast of the model (.double(), .to(torch.bfloat16)) reaches the
-        bias only. e4m3 -> any wider float -> e4m3 is exact."""
+        bias only. e4m3 -> any wider float -> e4m3 is exact; a floating-point
+        cast leaves MXFP4's integer buffers alone, and an explicit cast to
+        another integer type is undone here."""
         super()._apply(fn, recurse)
-        self.codes = self.codes.to(torch.float8_e4m3fn)
-        self.scale = self.scale.to(torch.float32)
+        for name, dtype in zip(("codes", self._SCALE), self._DTYPES):
+            setattr(self, name, getattr(self, name).to(dtype))
         return self
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features="
+                f"{self.out_features}, bias={self.bias is not None}")
+
+
+class W8Linear(_QuantLinear):
+    """A linear whose weight is e4m3 `codes` [out, in] and fp32 `scale` [out]
+    (buffers, as is the optional `bias`): forward is ops.linear_w8."""
+
+    _SCALE, _DTYPES = "scale", (torch.float8_e4m3fn, torch.float32)
+    _quantize = staticmethod(ops.torch_ref.weight_quantize)
+
+    def __init__(self, codes, scale, bias=None):
+        super().__init__(codes, scale, bias)
+        self.out_features, self.in_features = codes.shape
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return ops.linear_w8(x, self.codes, self.scale, self.bias)
 
-    def extra_repr(self) -> str:
-        return (f"in_features={self.in_features}, out_features="
-                f"{self.out_features}, bias={self.bias is not None}")
 
-
-class W4Linear(nn.Module):
+class W4Linear(_QuantLinear):
     """A linear whose weight is MXFP4: uint8 `codes` [out, in / 2] and uint8
     `scales` [out, in / 32] (buffers, as is the optional `bias`): forward is
     ops.linear_w4. in_features must be a multiple of 32."""
 
-    def __init__(self, codes: torch.Tensor, scales: torch.Tensor,
-                 bias: Optional[torch.Tensor] = None):
-        super().__init__()
+    _SCALE, _DTYPES = "scales", (torch.uint8, torch.uint8)
+    _quantize = staticmethod(ops.torch_ref.weight_quantize_mxfp4)
+
+    def __init__(self, codes, scales, bias=None):
+        super().__init__(codes, scales, bias)
         self.out_features, self.in_features = codes.shape[0], 2 * codes.shape[1]
-        self.register_buffer("codes", codes)
-        self.register_buffer("scales", scales)
-        self.register_buffer("bias", bias)
-
-    @classmethod
-    def from_linear(cls, lin: nn.Linear) -> "W4Linear":
-        codes, scales = ops.torch_ref.weight_quantize_mxfp4(lin.weight.detach())
-        bias = None if lin.bias is None else lin.bias.detach()
-        return cls(codes, scales, bias)
-
-    def _apply(self, fn, recurse=True):
-        """Moves and casts as any module, but the weight keeps its format: a
-        dtype cast of the model reaches the bias only. The buffers are
-        integers, which a floating-point cast leaves alone; an explicit cast
-        to another integer type is undone here."""
-        super()._apply(fn, recurse)
-        self.codes = self.codes.to(torch.uint8)
-        self.scales = self.scales.to(torch.uint8)
-        return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return ops.linear_w4(x, self.codes, self.scales, self.bias)
-
-    def extra_repr(self) -> str:
-        return (f"in_features={self.in_features}, out_features="
-                f"{self.out_features}, bias={self.bias is not None}")
 
 
 FP4 = torch.float4_e2m1fn_x2

@@ -377,6 +377,33 @@ def extend_attention_splits(bhkv: int, cols: int,
 
 
 W8_MAX_ROWS = 64      # the most rows of x the linear_w8 kernel takes
+W4_MAX_ROWS = 64      # the most rows of x the linear_w4 kernel takes
+
+
+def _skinny_linear(op, x, weight, bias, code_dtype, k_mult, max_rows, wide):
+    """linear_w8 / linear_w4 (`op`) on weight = (codes, scale(s)): torch_ref's
+    `op` outside the kernel's dtypes and K, `wide` for M > max_rows, else the
+    extension's `op` on x re-strided to its contract."""
+    K, N = x.shape[-1], weight[0].shape[0]
+    if (_use_ref(x) or x.dtype != torch.bfloat16
+            or weight[0].dtype != code_dtype or K % k_mult != 0 or K == 0):
+        return getattr(torch_ref, op)(x, *weight, bias)
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    if M == 0:
+        return x.new_empty(*x.shape[:-1], N)
+    if M > max_rows:
+        return wide(x2, *weight, bias).view(*x.shape[:-1], N)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    return getattr(hip_ext(), op)(x2, *weight, bias).view(*x.shape[:-1], N)
+
+
+def _linear_w8_wide(x2, codes, scale, bias):
+    y = torch.matmul(x2, codes.to(x2.dtype).t()).float() * scale
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x2.dtype)
 
 
 def linear_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
@@ -395,23 +422,8 @@ def linear_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
     bf16 rounding than the kernel, on the unscaled product, and N·K bf16
     elements of scratch per call. CPU tensors, other dtypes, other K and
     ACCO_FORCE_REF=1 run the torch reference."""
-    K, N = x.shape[-1], codes.shape[0]
-    if (_use_ref(x) or x.dtype != torch.bfloat16
-            or codes.dtype != FP8 or K % 64 != 0 or K == 0):
-        return torch_ref.linear_w8(x, codes, scale, bias)
-    x2 = x.reshape(-1, K)
-    M = x2.shape[0]
-    if M == 0:
-        return x.new_empty(*x.shape[:-1], N)
-    if M > W8_MAX_ROWS:
-        y = torch.matmul(x2, codes.to(x.dtype).t()).float() * scale
-        if bias is not None:
-            y = y + bias.float()
-        return y.to(x.dtype).view(*x.shape[:-1], N)
-    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
-        x2 = x2.contiguous()
-    y = hip_ext().linear_w8(x2, codes, scale, bias)
-    return y.view(*x.shape[:-1], N)
+    return _skinny_linear("linear_w8", x, (codes, scale), bias, FP8, 64,
+                          W8_MAX_ROWS, _linear_w8_wide)
 
 
 def linear_w8_splits(m: int, n: int, k: int) -> Tuple[int, int]:
@@ -423,7 +435,12 @@ def linear_w8_splits(m: int, n: int, k: int) -> Tuple[int, int]:
     return int(n_split), int(k_chunk)
 
 
-W4_MAX_ROWS = 64      # the most rows of x the linear_w4 kernel takes
+def _linear_w4_wide(x2, codes, scales, bias):
+    w = torch_ref.weight_dequantize_mxfp4(codes, scales, x2.dtype)
+    y = torch.matmul(x2, w.t())
+    if bias is not None:
+        y = (y.float() + bias.float()).to(x2.dtype)
+    return y
 
 
 def linear_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
@@ -443,24 +460,8 @@ def linear_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
     in fp32: one more bf16 rounding than the kernel and N·K bf16 elements of
     scratch per call. CPU tensors, other dtypes, other K and ACCO_FORCE_REF=1
     run the torch reference."""
-    K, N = x.shape[-1], codes.shape[0]
-    if (_use_ref(x) or x.dtype != torch.bfloat16
-            or codes.dtype != torch.uint8 or K % 128 != 0 or K == 0):
-        return torch_ref.linear_w4(x, codes, scales, bias)
-    x2 = x.reshape(-1, K)
-    M = x2.shape[0]
-    if M == 0:
-        return x.new_empty(*x.shape[:-1], N)
-    if M > W4_MAX_ROWS:
-        w = torch_ref.weight_dequantize_mxfp4(codes, scales, x.dtype)
-        y = torch.matmul(x2, w.t())
-        if bias is not None:
-            y = (y.float() + bias.float()).to(x.dtype)
-        return y.view(*x.shape[:-1], N)
-    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
-        x2 = x2.contiguous()
-    y = hip_ext().linear_w4(x2, codes, scales, bias)
-    return y.view(*x.shape[:-1], N)
+    return _skinny_linear("linear_w4", x, (codes, scales), bias, torch.uint8,
+                          128, W4_MAX_ROWS, _linear_w4_wide)
 
 
 def linear_w4_splits(m: int, n: int, k: int) -> Tuple[int, int]:

@@ -1328,33 +1328,86 @@ at::Tensor attn_extend_fp8(at::Tensor q, at::Tensor k_cache,
                          scale, window);
 }
 
-// ---- weight-only e4m3 linear for decode (linear_w8.hip)
-static void check_w8_sizes(int64_t M, int64_t N, int64_t K) {
-  TORCH_CHECK(M >= 1 && M <= 64 && N >= 1 && N < (1LL << 24) && K >= 64 &&
-              K < (1LL << 24) && K % 64 == 0,
-              "linear_w8: need 1 <= M <= 64, 1 <= N < 2^24 and K < 2^24 a "
-              "positive multiple of 64, got M=", M, " N=", N, " K=", K);
+// ---- weight-only linears for decode (linear_w8.hip, linear_w4.hip)
+static void check_skinny_sizes(const char* op, int64_t k_mult, int64_t M,
+                               int64_t N, int64_t K) {
+  TORCH_CHECK(M >= 1 && M <= 64 && N >= 1 && N < (1LL << 24) && K >= k_mult &&
+              K < (1LL << 24) && K % k_mult == 0,
+              op, ": need 1 <= M <= 64, 1 <= N < 2^24 and K < 2^24 a "
+              "positive multiple of ", k_mult, ", got M=", M, " N=", N, " K=",
+              K);
 }
 
-// (n_split, k_chunk) of linear_w8 for its three sizes: split i owns the
-// columns [i*k_chunk, (i+1)*k_chunk) of x and of the codes
-std::vector<int64_t> linear_w8_grid(int64_t M, int64_t N, int64_t K) {
-  check_w8_sizes(M, N, K);
+using skinny_grid_fn = void (*)(int, int, int, int*, int*);
+
+// (n_split, k_chunk) of a linear for its three sizes: split i owns the
+// columns [i*k_chunk, (i+1)*k_chunk) of x and of the weight
+static std::vector<int64_t> skinny_grid(skinny_grid_fn grid, int64_t M,
+                                        int64_t N, int64_t K) {
   int n_split, k_chunk;
-  acco_linear_w8_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
+  grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
   return {n_split, k_chunk};
+}
+
+std::vector<int64_t> linear_w8_grid(int64_t M, int64_t N, int64_t K) {
+  check_skinny_sizes("linear_w8", 64, M, N, K);
+  return skinny_grid(acco_linear_w8_grid, M, N, K);
+}
+
+std::vector<int64_t> linear_w4_grid(int64_t M, int64_t N, int64_t K) {
+  check_skinny_sizes("linear_w4", 128, M, N, K);
+  return skinny_grid(acco_linear_w4_grid, M, N, K);
+}
+
+static void check_skinny_x(const at::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
+              "x must be CUDA bf16 [M, K], got ", x.scalar_type(), " ",
+              x.sizes(), " on ", x.device());
+}
+
+// The x and bias contract of both linears: x rows stride(0) >= K apart (a
+// multiple of 8) with a contiguous last dim; bias, when given, contiguous
+// bf16 [N] on x's device. Returns the row stride.
+static int64_t check_skinny_x_bias(const at::Tensor& x, int64_t N,
+                                   const c10::optional<at::Tensor>& bias) {
+  const int64_t M = x.size(0), K = x.size(1);
+  const int64_t rs = M > 1 ? x.stride(0) : K;
+  TORCH_CHECK(x.stride(1) == 1 && rs >= K && rs % 8 == 0,
+              "x must have a contiguous last dim and rows a multiple of 8 "
+              "elements, at least K, apart, got strides ", x.strides());
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                bias->scalar_type() == at::kBFloat16 &&
+                bias->is_contiguous() && bias->dim() == 1 &&
+                bias->size(0) == N, "bias must be contiguous bf16 [N] = [", N,
+                "] on ", x.device(), ", got ", bias->scalar_type(), " ",
+                bias->sizes(), " on ", bias->device());
+  return rs;
+}
+
+// The shared tail: y and the partials' workspace for the op's grid, then
+// launch(y, workspace) and the launch check.
+template <class Launch>
+static at::Tensor skinny_run(skinny_grid_fn grid, const at::Tensor& x,
+                             int64_t N, Launch launch) {
+  const int64_t M = x.size(0);
+  const int64_t n_split = skinny_grid(grid, M, N, x.size(1))[0];
+  auto y = at::empty({M, N}, x.options());
+  auto ws = at::empty({n_split > 1 ? n_split * M * N : 0},
+                      x.options().dtype(at::kFloat));
+  launch(y.data_ptr(), ws.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return y;
 }
 
 // y [M, N] bf16 = x . codes^T * scale (+ bias). The argument contract: x CUDA
 // bf16 [M, K] with a contiguous last dim, rows stride(0) >= K apart (a
 // multiple of 8) on a 16-byte aligned base; codes contiguous float8_e4m3fn
 // [N, K], 16-byte aligned; scale contiguous fp32 [N]; bias, when given,
-// contiguous bf16 [N]; all on x's device; sizes as check_w8_sizes.
+// contiguous bf16 [N]; all on x's device; sizes as check_skinny_sizes.
 at::Tensor linear_w8(at::Tensor x, at::Tensor codes, at::Tensor scale,
                      c10::optional<at::Tensor> bias) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
-              "x must be CUDA bf16 [M, K], got ", x.scalar_type(), " ",
-              x.sizes(), " on ", x.device());
+  check_skinny_x(x);
   TORCH_CHECK(codes.is_cuda() && codes.device() == x.device() &&
               codes.scalar_type() == at::kFloat8_e4m3fn &&
               codes.is_contiguous() && codes.dim() == 2 &&
@@ -1363,63 +1416,26 @@ at::Tensor linear_w8(at::Tensor x, at::Tensor codes, at::Tensor scale,
               "] on ", x.device(), ", got ", codes.scalar_type(), " ",
               codes.sizes(), " on ", codes.device());
   const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
-  check_w8_sizes(M, N, K);
-  const int64_t rs = M > 1 ? x.stride(0) : K;
-  TORCH_CHECK(x.stride(1) == 1 && rs >= K && rs % 8 == 0,
-              "x must have a contiguous last dim and rows a multiple of 8 "
-              "elements, at least K, apart, got strides ", x.strides());
+  check_skinny_sizes("linear_w8", 64, M, N, K);
   TORCH_CHECK(aligned_to(x, 16) && aligned_to(codes, 16),
               "x and codes must be 16-byte aligned");
   check_f32_vec(scale, N, x, "scale");
   TORCH_CHECK(scale.dim() == 1, "scale must be [N], got ", scale.sizes());
-  if (bias.has_value())
-    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
-                bias->scalar_type() == at::kBFloat16 &&
-                bias->is_contiguous() && bias->dim() == 1 &&
-                bias->size(0) == N, "bias must be contiguous bf16 [N] = [", N,
-                "] on ", x.device(), ", got ", bias->scalar_type(), " ",
-                bias->sizes(), " on ", bias->device());
-  int n_split, k_chunk;
-  acco_linear_w8_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
-  auto y = at::empty({M, N}, x.options());
-  auto ws = at::empty({n_split > 1 ? n_split * M * N : 0},
-                      x.options().dtype(at::kFloat));
-  acco_linear_w8(x.data_ptr(), codes.data_ptr(), scale.data_ptr<float>(),
-                 bias.has_value() ? bias->data_ptr() : nullptr, y.data_ptr(),
-                 ws.data_ptr<float>(), (int)M, (int)N, (int)K, rs,
-                 cur_stream());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  return y;
-}
-
-// ---- weight-only MXFP4 linear for decode (linear_w4.hip)
-static void check_w4_sizes(int64_t M, int64_t N, int64_t K) {
-  TORCH_CHECK(M >= 1 && M <= 64 && N >= 1 && N < (1LL << 24) && K >= 128 &&
-              K < (1LL << 24) && K % 128 == 0,
-              "linear_w4: need 1 <= M <= 64, 1 <= N < 2^24 and K < 2^24 a "
-              "positive multiple of 128, got M=", M, " N=", N, " K=", K);
-}
-
-// (n_split, k_chunk) of linear_w4 for its three sizes: split i owns the
-// columns [i*k_chunk, (i+1)*k_chunk) of x and of the weight
-std::vector<int64_t> linear_w4_grid(int64_t M, int64_t N, int64_t K) {
-  check_w4_sizes(M, N, K);
-  int n_split, k_chunk;
-  acco_linear_w4_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
-  return {n_split, k_chunk};
+  const int64_t rs = check_skinny_x_bias(x, N, bias);
+  return skinny_run(acco_linear_w8_grid, x, N, [&](void* y, float* ws) {
+    acco_linear_w8(x.data_ptr(), codes.data_ptr(), scale.data_ptr<float>(),
+                   bias.has_value() ? bias->data_ptr() : nullptr, y, ws,
+                   (int)M, (int)N, (int)K, rs, cur_stream());
+  });
 }
 
 // y [M, N] bf16 = x . dequant(codes, scales)^T (+ bias). The argument
-// contract: x CUDA bf16 [M, K] with a contiguous last dim, rows stride(0) >= K
-// apart (a multiple of 8) on a 16-byte aligned base; codes contiguous uint8
-// [N, K / 2] (two e2m1 per byte), 16-byte aligned; scales contiguous uint8
-// [N, K / 32] (e8m0), 4-byte aligned; bias, when given, contiguous bf16 [N];
-// all on x's device; sizes as check_w4_sizes.
+// contract: x and bias as linear_w8's; codes contiguous uint8 [N, K / 2] (two
+// e2m1 per byte), 16-byte aligned; scales contiguous uint8 [N, K / 32]
+// (e8m0), 4-byte aligned; all on x's device; sizes as check_skinny_sizes.
 at::Tensor linear_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
                      c10::optional<at::Tensor> bias) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
-              "x must be CUDA bf16 [M, K], got ", x.scalar_type(), " ",
-              x.sizes(), " on ", x.device());
+  check_skinny_x(x);
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(codes.is_cuda() && codes.device() == x.device() &&
               codes.scalar_type() == at::kByte && codes.is_contiguous() &&
@@ -1428,7 +1444,7 @@ at::Tensor linear_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
               x.device(), ", got ", codes.scalar_type(), " ", codes.sizes(),
               " on ", codes.device());
   const int64_t N = codes.size(0);
-  check_w4_sizes(M, N, K);
+  check_skinny_sizes("linear_w4", 128, M, N, K);
   TORCH_CHECK(scales.is_cuda() && scales.device() == x.device() &&
               scales.scalar_type() == at::kByte && scales.is_contiguous() &&
               scales.dim() == 2 && scales.size(0) == N &&
@@ -1436,31 +1452,15 @@ at::Tensor linear_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
               "scales must be contiguous uint8 [N, K / 32] = [", N, ", ",
               K / 32, "] on ", x.device(), ", got ", scales.scalar_type(), " ",
               scales.sizes(), " on ", scales.device());
-  const int64_t rs = M > 1 ? x.stride(0) : K;
-  TORCH_CHECK(x.stride(1) == 1 && rs >= K && rs % 8 == 0,
-              "x must have a contiguous last dim and rows a multiple of 8 "
-              "elements, at least K, apart, got strides ", x.strides());
   TORCH_CHECK(aligned_to(x, 16) && aligned_to(codes, 16) &&
               aligned_to(scales, 4),
               "x and codes must be 16-byte aligned, scales 4-byte aligned");
-  if (bias.has_value())
-    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
-                bias->scalar_type() == at::kBFloat16 &&
-                bias->is_contiguous() && bias->dim() == 1 &&
-                bias->size(0) == N, "bias must be contiguous bf16 [N] = [", N,
-                "] on ", x.device(), ", got ", bias->scalar_type(), " ",
-                bias->sizes(), " on ", bias->device());
-  int n_split, k_chunk;
-  acco_linear_w4_grid((int)M, (int)N, (int)K, &n_split, &k_chunk);
-  auto y = at::empty({M, N}, x.options());
-  auto ws = at::empty({n_split > 1 ? n_split * M * N : 0},
-                      x.options().dtype(at::kFloat));
-  acco_linear_w4(x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
-                 bias.has_value() ? bias->data_ptr() : nullptr, y.data_ptr(),
-                 ws.data_ptr<float>(), (int)M, (int)N, (int)K, rs,
-                 cur_stream());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  return y;
+  const int64_t rs = check_skinny_x_bias(x, N, bias);
+  return skinny_run(acco_linear_w4_grid, x, N, [&](void* y, float* ws) {
+    acco_linear_w4(x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+                   bias.has_value() ? bias->data_ptr() : nullptr, y, ws,
+                   (int)M, (int)N, (int)K, rs, cur_stream());
+  });
 }
 
 // ---- on-device sampling (sample.hip)

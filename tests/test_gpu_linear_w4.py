@@ -39,6 +39,45 @@ def check_splits(M, N, K):
     return n_split, k_chunk
 
 
+# (n_split, k_chunk) as the grid function gave them when the two kernels were
+# consolidated; rows M in PIN_M, columns N in PIN_N
+PIN_M, PIN_N = (1, 16, 17, 64), (1, 128, 129, 4096, 14336)
+PINNED = {
+    K_ONE: [
+        [(1, 512), (1, 512), (1, 512), (1, 512), (1, 512)],
+        [(1, 512), (1, 512), (1, 512), (1, 512), (1, 512)],
+        [(1, 512), (1, 512), (1, 512), (1, 512), (1, 512)],
+        [(1, 512), (1, 512), (1, 512), (1, 512), (1, 512)],
+    ],
+    K_SHORT: [
+        [(13, 512), (13, 512), (13, 512), (13, 512), (4, 2048)],
+        [(7, 1024), (7, 1024), (7, 1024), (7, 1024), (4, 2048)],
+        [(7, 1024), (7, 1024), (7, 1024), (7, 1024), (4, 2048)],
+        [(3, 2560), (3, 2560), (3, 2560), (3, 2560), (3, 2560)],
+    ],
+    K_MOST: [
+        [(64, 512), (64, 512), (64, 512), (16, 2048), (4, 8192)],
+        [(64, 512), (64, 512), (64, 512), (16, 2048), (4, 8192)],
+        [(32, 1024), (32, 1024), (32, 1024), (16, 2048), (4, 8192)],
+        [(16, 2048), (16, 2048), (16, 2048), (16, 2048), (4, 8192)],
+    ],
+    69632: [
+        [(46, 1536), (46, 1536), (46, 1536), (16, 4608), (4, 17408)],
+        [(46, 1536), (46, 1536), (46, 1536), (16, 4608), (4, 17408)],
+        [(46, 1536), (46, 1536), (46, 1536), (16, 4608), (4, 17408)],
+        [(34, 2048), (34, 2048), (34, 2048), (16, 4608), (4, 17408)],
+    ],
+}
+
+
+def test_splits_pinned():
+    """The grid is a host function of its three sizes: a refactor keeps it."""
+    for K, rows in PINNED.items():
+        for M, row in zip(PIN_M, rows):
+            for N, want in zip(PIN_N, row):
+                assert ops.linear_w4_splits(M, N, K) == want, (M, N, K)
+
+
 def make(M, N, K, name):
     g = case_generator("linear_w4_%s_%d_%d_%d" % (name, M, N, K))
     h = torch.randn(M, 2, K, generator=g).bfloat16().to(DEV)

@@ -40,6 +40,45 @@ def check_splits(M, N, K):
     return n_split, k_chunk
 
 
+# (n_split, k_chunk) as the grid function gave them when the two kernels were
+# consolidated; rows M in PIN_M, columns N in PIN_N
+PIN_M, PIN_N = (1, 16, 17, 64), (1, 128, 129, 4096, 14336)
+PINNED = {
+    K_ONE: [
+        [(1, 64), (1, 64), (1, 64), (1, 64), (1, 64)],
+        [(1, 64), (1, 64), (1, 64), (1, 64), (1, 64)],
+        [(1, 64), (1, 64), (1, 64), (1, 64), (1, 64)],
+        [(1, 64), (1, 64), (1, 64), (1, 64), (1, 64)],
+    ],
+    K_SHORT: [
+        [(50, 128), (50, 128), (50, 128), (15, 448), (4, 1600)],
+        [(20, 320), (20, 320), (20, 320), (15, 448), (4, 1600)],
+        [(20, 320), (20, 320), (20, 320), (15, 448), (4, 1600)],
+        [(6, 1088), (6, 1088), (6, 1088), (6, 1088), (4, 1600)],
+    ],
+    K_MOST: [
+        [(64, 64), (64, 64), (64, 64), (16, 256), (4, 1024)],
+        [(16, 256), (16, 256), (16, 256), (16, 256), (4, 1024)],
+        [(13, 320), (13, 320), (13, 320), (13, 320), (4, 1024)],
+        [(4, 1024), (4, 1024), (4, 1024), (4, 1024), (4, 1024)],
+    ],
+    69632: [
+        [(64, 1088), (64, 1088), (64, 1088), (16, 4352), (4, 17408)],
+        [(64, 1088), (64, 1088), (64, 1088), (16, 4352), (4, 17408)],
+        [(64, 1088), (64, 1088), (64, 1088), (16, 4352), (4, 17408)],
+        [(64, 1088), (64, 1088), (64, 1088), (16, 4352), (4, 17408)],
+    ],
+}
+
+
+def test_splits_pinned():
+    """The grid is a host function of its three sizes: a refactor keeps it."""
+    for K, rows in PINNED.items():
+        for M, row in zip(PIN_M, rows):
+            for N, want in zip(PIN_N, row):
+                assert ops.linear_w8_splits(M, N, K) == want, (M, N, K)
+
+
 def make(M, N, K, name):
     g = case_generator("linear_w8_%s_%d_%d_%d" % (name, M, N, K))
     h = torch.randn(M, 2, K, generator=g).bfloat16().to(DEV)
