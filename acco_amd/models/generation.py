@@ -23,7 +23,8 @@ def generate(model, input_ids: torch.Tensor,
              seed: int = 0, eos_token_id: Optional[int] = None,
              prefill_chunk: int = 0,
              kv_dtype: Optional[torch.dtype] = None,
-             weight_dtype: Optional[torch.dtype] = None
+             weight_dtype: Optional[torch.dtype] = None,
+             draft=None, spec_k: int = 4
              ) -> Tuple[torch.Tensor, torch.Tensor]:
     """(tokens int64 [B, S + max_new], n_generated int64 [B]) for prompts
     `input_ids` [B, S] of `model` (LlamaForCausalLM or GPTNeoForCausalLM, in
@@ -51,7 +52,16 @@ def generate(model, input_ids: torch.Tensor,
     used as it is). torch.float4_e2m1fn_x2 does the same in OCP MXFP4
     (quantize_weights(model, dtype), ops.linear_w4): e2m1 codes with one
     power-of-two scale per 32 weights, about 0.53 bytes per weight; a model
-    that already holds quantised linears of either kind is used as it is."""
+    that already holds quantised linears of either kind is used as it is.
+    draft: a model of the same interface and vocab_size (for one,
+    quantize_weights(model, torch.float4_e2m1fn_x2) of `model` itself) turns
+    on speculative decoding, spec_k >= 1 drafted tokens per round
+    (_generate_speculative has the loop): the tokens are distributed as
+    without a draft, and greedy ones are the target's own argmax of the logits
+    it computes; the draws differ from the plain loop's for the same seed.
+    top_k / top_p are not supported with a draft (ValueError); weight_dtype
+    applies to `model` only; needs S + max_new + spec_k + 1 <=
+    max_position_embeddings of both models. None: the loop above, unchanged."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B, S], got {input_ids.shape}")
     if weight_dtype is not None:
@@ -78,6 +88,8 @@ def generate(model, input_ids: torch.Tensor,
     elif not 0 <= int(eos_token_id) < cfg.vocab_size:
         raise ValueError(f"eos_token_id must be in [0, {cfg.vocab_size}), "
                          f"got {eos_token_id}")
+    if draft is not None:
+        _check_draft(model, draft, spec_k, top_k, top_p, S + max_new)
     dev = input_ids.device
     total = S + max_new
     if lens is None:
@@ -94,6 +106,11 @@ def generate(model, input_ids: torch.Tensor,
     done = None
     if eos_token_id is not None:
         done = torch.zeros(B, device=dev, dtype=torch.uint8)
+    if draft is not None:
+        return _generate_speculative(
+            model, draft, int(spec_k), input_ids, lens, start, tokens, done,
+            max_new, float(temperature), seed, eos_token_id,
+            int(prefill_chunk), kv_dtype)
     cache = KVCache.allocate(model, B, total, dtype=kv_dtype)
     if 0 < int(prefill_chunk) < S:
         logits = prefill_chunked(model, input_ids, lens, cache, prefill_chunk)
@@ -112,3 +129,107 @@ def generate(model, input_ids: torch.Tensor,
         if i + 1 < max_new:
             logits = model.decode_step(tok, cache)
     return tokens, n_generated
+
+
+def _check_draft(model, draft, spec_k, top_k, top_p, total: int) -> None:
+    if int(top_k) != 0 or float(top_p) < 1.0:
+        raise ValueError("generate(draft=...) supports neither top_k nor "
+                         "top_p: the verification compares unfiltered "
+                         "distributions")
+    if int(spec_k) < 1:
+        raise ValueError(f"spec_k must be >= 1, got {spec_k}")
+    for name in ("prefill", "decode_step", "extend"):
+        if not callable(getattr(draft, name, None)):
+            raise ValueError(f"draft has no {name}(): it must be a model of "
+                             "the same interface as the target")
+    v_d = getattr(getattr(draft, "cfg", None), "vocab_size", None)
+    if v_d != model.cfg.vocab_size:
+        raise ValueError(f"draft vocab_size {v_d} is not the target's "
+                         f"{model.cfg.vocab_size}")
+    need = total + int(spec_k) + 1
+    for m in (model, draft):
+        if need > int(m.cfg.max_position_embeddings):
+            raise ValueError(
+                f"speculative decoding needs S + max_new + spec_k + 1 = "
+                f"{need} <= max_position_embeddings = "
+                f"{m.cfg.max_position_embeddings}")
+
+
+def _generate_speculative(model, draft, k, input_ids, lens, start, tokens,
+                          done, max_new, temperature, seed, eos_token_id,
+                          prefill_chunk, kv_dtype):
+    """The loop of generate(draft=...). State per sequence b: n[b] tokens
+    produced, both caches valid below L[b] = start[b] - 1 + n[b], last[b] the
+    token at position L[b] (at first the prompt's last token: its cache row is
+    written again by round 0). A round:
+      1  the draft takes k decode_step + sample_logits from last, keeping its
+         k logits rows, and one more decode_step on x_{k-1}, so that its
+         cache covers positions L .. L + k like the target's;
+      2  the target scores [last, x_0 .. x_{k-1}] in one extend with
+         n_new = 0 (its lens stay): p_0 .. p_k;
+      3  ops.spec_verify: n_accept drafted tokens and the token after them;
+      4  those n_accept + 1 tokens go to columns start + n .., on the device;
+         writes stop at the sequence's first eos and at column
+         start + max_new, and a sequence that is done or full does not move;
+      5  both caches are set to the new L; their rows beyond it are stale and
+         are overwritten by the next round (the argument of right-padding).
+    The host cannot know n, so it reads one int64 [2] per round: min n (done
+    sequences count as full) ends the loop at max_new, max n bounds the
+    caches' host-side step count. Draft draws use generator steps r k + j,
+    the verification step r, in its own counter range."""
+    B, S = input_ids.shape
+    dev = input_ids.device
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    rows = S + max_new + k + 1
+    caches = [KVCache.allocate(m, B, rows, dtype=kv_dtype)
+              for m in (model, draft)]
+    for m, c in zip((model, draft), caches):
+        if 0 < prefill_chunk < S:
+            prefill_chunked(m, input_ids, lens, c, prefill_chunk)
+        else:
+            m.prefill(input_ids, lens, c)
+    # one spare column takes the masked writes
+    out = torch.cat([tokens, tokens[:, :1]], dim=1)
+    spare = out.shape[1] - 1
+    n = torch.zeros(B, device=dev, dtype=torch.long)
+    last = input_ids.gather(1, (start - 1)[:, None])[:, 0]
+    j = torch.arange(k + 1, device=dev)[None, :]
+    zero = torch.zeros(B, device=dev, dtype=torch.int32)
+    n_max, r = 0, 0
+    while True:
+        for c in caches:
+            c.begin(S - 1 + n_max, start - 1 + n)
+        tok, xs, q_rows = last, [], []
+        for i in range(k):
+            q_rows.append(draft.decode_step(tok, caches[1]))
+            tok = ops.sample_logits(q_rows[-1], temperature=temperature,
+                                    seed=seed, step=r * k + i)[0]
+            xs.append(tok)
+        draft.decode_step(tok, caches[1])
+        xs = torch.stack(xs, dim=1)                               # [B, k]
+        p_logits = model.extend(torch.cat([last[:, None], xs], dim=1),
+                                caches[0], n_new=zero)
+        was_done = None if done is None else done != 0
+        n_accept, nxt, _ = ops.spec_verify(
+            p_logits, torch.stack(q_rows, dim=1), xs,
+            temperature=temperature, seed=seed, step=r, done=done, eos_id=eos)
+        new = torch.cat([xs, nxt[:, None]], dim=1)
+        new = torch.where(j == n_accept[:, None], nxt[:, None], new)
+        write = (j <= n_accept[:, None]) & (j < (max_new - n)[:, None])
+        if done is not None:
+            write &= ~was_done[:, None]
+            hit = (new == eos) & write
+            write &= (hit.cumsum(1) - hit.long()) == 0     # up to the first eos
+            done.copy_(was_done | (hit & write).any(1))
+        cols = torch.where(write, (start + n)[:, None] + j, spare)
+        out.scatter_(1, cols, new)
+        adv = write.sum(1)
+        last = torch.where(adv > 0,
+                           new.gather(1, (adv - 1).clamp(min=0)[:, None])[:, 0],
+                           last)
+        n = n + adv
+        full = n if done is None else torch.where(done != 0, max_new, n)
+        n_min, n_max = torch.stack([full.min(), n.max()]).tolist()
+        r += 1
+        if n_min >= max_new:
+            return out[:, :spare].contiguous(), n

@@ -499,6 +499,39 @@ def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
     return token, logprob, thr, n_kept
 
 
+def spec_verify(p_logits: torch.Tensor, q_logits: torch.Tensor,
+                draft_tokens: torch.Tensor, *, temperature: float, seed: int,
+                step: int, done: Optional[torch.Tensor] = None,
+                eos_id: int = -1
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The accept / reject / resample step of speculative decoding, on the
+    logits' device: target logits p_logits [B, k+1, V], draft logits q_logits
+    [B, k, V] and the k drafted tokens int64 [B, k] give (n_accept int32 [B]
+    in [0, k], next_token int64 [B] in [0, V), accept_prob fp32 [B, k]): the
+    drafted tokens accepted before the first rejection, and the token that
+    follows them, drawn from the residual max(p - q, 0) of the rejecting row
+    or from p_k when every token was accepted, so that the emitted tokens are
+    distributed as the target's own samples. temperature == 0 accepts a token
+    iff it is the target's argmax. The draws come from a counter-based
+    generator keyed by (seed, step, row, index) in a range that no
+    sample_logits call can reach: a pure function of the arguments, bitwise
+    reproducible. `done` and `eos_id` as for sample_logits: a finished row
+    gives n_accept 0 and next_token eos_id (torch_ref.spec_verify has the
+    semantics). Two HIP kernels for bf16 on the GPU (spec_verify.hip), no
+    softmax tensor and no host read; the fp64 reference for CPU tensors,
+    other dtypes and ACCO_FORCE_REF=1."""
+    if (_use_ref(p_logits) or p_logits.dtype != torch.bfloat16
+            or q_logits.dtype != torch.bfloat16):
+        return torch_ref.spec_verify(
+            p_logits, q_logits, draft_tokens, temperature=temperature,
+            seed=seed, step=step, done=done, eos_id=eos_id)
+    mask = (1 << 64) - 1
+    n_accept, next_token, accept_prob = hip_ext().spec_verify(
+        p_logits, q_logits, draft_tokens, float(temperature),
+        int(seed) & mask, int(step) & mask, done, int(eos_id))
+    return n_accept, next_token, accept_prob
+
+
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     if _use_ref(logits, "ce_fwd"):
         return torch_ref.causal_lm_loss(logits, labels)

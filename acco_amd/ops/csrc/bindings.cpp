@@ -1526,9 +1526,99 @@ std::vector<at::Tensor> sample_logits(at::Tensor logits, double temperature,
   return {token, logprob, thr, n_kept};
 }
 
+// ---- draft verification (spec_verify.hip)
+// (n_accept int32 [B], next_token int64 [B], accept_prob fp32 [B, k]). The
+// argument contract: p_logits CUDA bf16 [B, k+1, V] and q_logits [B, k, V] on
+// the same device, k >= 1, 1 <= V < 2^31, B (k + 1) < 2^31, the last dim
+// contiguous and rows at least V elements apart (no alignment asked);
+// draft_tokens contiguous int64 [B, k] on that device; temperature finite and
+// >= 0 (0 = greedy); done and eos_id as for sample_logits.
+std::vector<at::Tensor> spec_verify(at::Tensor p_logits, at::Tensor q_logits,
+                                    at::Tensor draft_tokens,
+                                    double temperature, uint64_t seed,
+                                    uint64_t step,
+                                    c10::optional<at::Tensor> done,
+                                    int64_t eos_id) {
+  TORCH_CHECK(p_logits.is_cuda() && p_logits.scalar_type() == at::kBFloat16 &&
+              q_logits.scalar_type() == at::kBFloat16 &&
+              q_logits.device() == p_logits.device(),
+              "p_logits and q_logits must be CUDA bf16 on one device, got ",
+              p_logits.scalar_type(), " on ", p_logits.device(), " and ",
+              q_logits.scalar_type(), " on ", q_logits.device());
+  TORCH_CHECK(p_logits.dim() == 3 && q_logits.dim() == 3 &&
+              p_logits.size(1) >= 2 && p_logits.size(2) >= 1 &&
+              p_logits.size(2) < (1LL << 31) &&
+              q_logits.size(0) == p_logits.size(0) &&
+              q_logits.size(1) == p_logits.size(1) - 1 &&
+              q_logits.size(2) == p_logits.size(2),
+              "need p_logits [B, k+1, V] and q_logits [B, k, V] with k >= 1 "
+              "and 1 <= V < 2^31, got ", p_logits.sizes(), " and ",
+              q_logits.sizes());
+  const int64_t B = p_logits.size(0), k = q_logits.size(1),
+                V = p_logits.size(2);
+  TORCH_CHECK(B * (k + 1) < (1LL << 31), "B (k + 1) must be below 2^31, got ",
+              p_logits.sizes());
+  for (const at::Tensor* t : {&p_logits, &q_logits}) {
+    TORCH_CHECK(V == 1 || t->stride(2) == 1,
+                "logits: the last dim must be contiguous, got strides ",
+                t->strides());
+    TORCH_CHECK((t->size(1) == 1 || t->stride(1) >= V) &&
+                (B <= 1 || t->stride(0) >= V),
+                "logits: rows must not overlap (strides >= V = ", V,
+                "), got strides ", t->strides());
+  }
+  TORCH_CHECK(draft_tokens.device() == p_logits.device() &&
+              draft_tokens.scalar_type() == at::kLong &&
+              draft_tokens.is_contiguous() && draft_tokens.dim() == 2 &&
+              draft_tokens.size(0) == B && draft_tokens.size(1) == k,
+              "draft_tokens must be contiguous int64 [B, k] = [", B, ", ", k,
+              "] on ", p_logits.device(), ", got ",
+              draft_tokens.scalar_type(), " ", draft_tokens.sizes(), " on ",
+              draft_tokens.device());
+  TORCH_CHECK(temperature >= 0.0 && temperature < 1e30,
+              "temperature must be finite and >= 0, got ", temperature);
+  TORCH_CHECK(temperature == 0.0 || (float)temperature > 0.0f,
+              "temperature underflows fp32: ", temperature);
+  unsigned char* done_ptr = nullptr;
+  if (done.has_value()) {
+    TORCH_CHECK(done->is_cuda() && done->device() == p_logits.device() &&
+                done->scalar_type() == at::kByte && done->is_contiguous() &&
+                done->dim() == 1 && done->size(0) == B,
+                "done must be contiguous uint8 [B] = [", B, "] on ",
+                p_logits.device(), ", got ", done->scalar_type(), " ",
+                done->sizes(), " on ", done->device());
+    TORCH_CHECK(eos_id >= 0 && eos_id < V, "with done, eos_id must be in "
+                "[0, V = ", V, "), got ", eos_id);
+    done_ptr = done->data_ptr<unsigned char>();
+  }
+  auto opts = p_logits.options();
+  auto n_accept = at::empty({B}, opts.dtype(at::kInt));
+  auto next_token = at::empty({B}, opts.dtype(at::kLong));
+  auto accept_prob = at::empty({B, k}, opts.dtype(at::kFloat));
+  if (B == 0) return {n_accept, next_token, accept_prob};
+  auto ws = at::empty({B, k + 1, 2}, opts.dtype(at::kInt));
+  acco_spec_verify(p_logits.data_ptr(), B > 1 ? p_logits.stride(0) : 0,
+                   p_logits.stride(1), q_logits.data_ptr(),
+                   B > 1 ? q_logits.stride(0) : 0,
+                   k > 1 ? q_logits.stride(1) : 0,
+                   reinterpret_cast<const long long*>(
+                       draft_tokens.data_ptr<int64_t>()),
+                   (int)B, (int)k, (int)V, (float)temperature, seed, step,
+                   done_ptr, eos_id, n_accept.data_ptr<int>(),
+                   reinterpret_cast<long long*>(
+                       next_token.data_ptr<int64_t>()),
+                   accept_prob.data_ptr<float>(), ws.data_ptr<int>(),
+                   cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {n_accept, next_token, accept_prob};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("spec_verify", &spec_verify, py::arg("p_logits"),
+        py::arg("q_logits"), py::arg("draft_tokens"), py::arg("temperature"),
+        py::arg("seed"), py::arg("step"), py::arg("done"), py::arg("eos_id"));
   m.def("sample_logits", &sample_logits, py::arg("logits"),
         py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("step"), py::arg("done"),

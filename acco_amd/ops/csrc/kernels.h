@@ -211,6 +211,24 @@ void acco_sample_logits(const void* logits, long long row_stride, int B,
                         long long* token, float* logprob, void* thr,
                         int* n_kept, hipStream_t s);
 
+// ---- spec_verify.hip
+// Draft verification of speculative decoding: target logits p [B, k+1, V] and
+// draft logits q [B, k, V], bf16, batch / row strides in elements, the last
+// dim contiguous, any alignment; draft_tokens int64 [B, k] contiguous (a
+// token outside [0, V) rejects). Outputs by ordinary stores: n_accept int32
+// [B] in [0, k], next_token int64 [B] in [0, V), accept_prob fp32 [B, k].
+// workspace: int32 [B, k+1, 2], need not be cleared. temperature == 0 is the
+// greedy rule. done (uint8 [B], nullable): a set flag gives n_accept 0 and
+// next_token eos_id (in [0, V)) with nothing drawn, otherwise
+// done[b] = (next_token == eos_id). Two launches, bitwise reproducible.
+void acco_spec_verify(const void* p_logits, long long p_bs, long long p_ts,
+                      const void* q_logits, long long q_bs, long long q_ts,
+                      const long long* draft_tokens, int B, int k, int V,
+                      float temperature, unsigned long long seed,
+                      unsigned long long step, unsigned char* done,
+                      long long eos_id, int* n_accept, long long* next_token,
+                      float* accept_prob, int* workspace, hipStream_t s);
+
 // ---- gemm_nt.hip
 void acco_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K,
                   hipStream_t stream);

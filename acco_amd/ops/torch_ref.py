@@ -632,6 +632,160 @@ def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
             torch.from_numpy(n_kept).to(dev))
 
 
+# ------------------------------------- draft verification (speculative decoding)
+# The executable definition of ops.spec_verify (kernel: csrc/spec_verify.hip).
+
+SPEC_ROW_TAG = 0x80000000        # Philox word 1: no sampler row has bit 31
+SPEC_ACCEPT_WORD = 0xFFFFFFFF    # Philox word 0 of u_t: no index reaches it
+
+
+def _spec_uniform(word0, word1, step: int, seed: int):
+    """sample_uniform at the Philox counter (word0, word1, step_lo, step_hi),
+    word0 and word1 broadcast against each other."""
+    import numpy as np
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    w0, w1 = np.broadcast_arrays(np.asarray(word0, dtype=np.uint64),
+                                 np.asarray(word1, dtype=np.uint64))
+    full = lambda v: np.full(w0.shape, v, dtype=np.uint64)   # noqa: E731
+    out = philox4x32_10((w0, w1, full(step & 0xFFFFFFFF), full(step >> 32)),
+                        (full(seed & 0xFFFFFFFF), full(seed >> 32)))[0]
+    return ((out >> np.uint64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+
+
+def _spec_softmax(key, T: float):
+    """(probabilities, (x - max) / T, sanitised x) of rows of keys [B, V] in
+    fp64; NaN (key 0) has mass 0, a row without a finite logit is all 0."""
+    import numpy as np
+    valid = key > 0
+    x = _bf16_bits_to_f64(sample_key_bits(key))
+    xmax = np.where(valid, x, -np.inf).max(axis=1, keepdims=True)
+    a = np.where(valid, (x - np.where(np.isfinite(xmax), xmax, 0.0)) / T, 0.0)
+    w = np.where(valid, np.exp(a), 0.0)
+    z = w.sum(axis=1, keepdims=True)
+    return w / np.where(z > 0, z, 1.0), a, x
+
+
+def spec_verify(p_logits: torch.Tensor, q_logits: torch.Tensor,
+                draft_tokens: torch.Tensor, *, temperature: float, seed: int,
+                step: int, done: Optional[torch.Tensor] = None,
+                eos_id: int = -1, details: Optional[list] = None):
+    """(n_accept int32 [B], next_token int64 [B], accept_prob fp32 [B, k]):
+    the accept / reject / resample step of speculative decoding over target
+    logits p_logits [B, k+1, V], draft logits q_logits [B, k, V] and the
+    drafted tokens x [B, k]. Logits are taken as bf16 and sanitised as the
+    sampler's (sample_keys: -0 -> +0, +-inf clamped, NaN has mass 0).
+
+    temperature > 0, p_t = softmax(p_logits[b, t] / T), q_t likewise (a row
+    without a finite logit is all 0): x_t is accepted iff
+    u_t · q_t(x_t) < p_t(x_t) (no division: q_t(x_t) = 0 is defined; a token
+    outside [0, V) has p = q = 0 and rejects); accept_prob[b, t] =
+    min(1, p_t(x_t) / q_t(x_t)), 0 when both are 0. n_accept = accepted tokens
+    before the first rejection. n_accept = t < k: next_token = argmax over i
+    with p_t(i) > q_t(i) of log(p_t(i) - q_t(i)) + g_i, lowest index on ties
+    (a Gumbel-max draw from the residual); an empty residual draws from p_t
+    as below. n_accept = k: next_token = argmax_i x_i / T + g_i over the
+    non-NaN i of p_k, the sampler's draw (0 without a finite logit).
+    temperature == 0: x_t is accepted iff it is the lowest-index argmax of
+    p row t, next_token is that argmax of row n_accept, accept_prob is 0 or
+    1, nothing is drawn.
+
+    Generator: Philox4x32-10 under key (seed_lo, seed_hi) at counter
+    (w0, 2^31 | (b (k + 1) + t), step_lo, step_hi): w0 = i for g_i of row
+    (b, t), w0 = 2^32 - 1 for u_t; both map the word as sample_uniform does,
+    g = -log(-log(u)). sample_logits uses (i, row, step_lo, step_hi) with
+    i, row < 2^31, so no call of it shares a counter with this one, whatever
+    the (seed, step). Needs B (k + 1) < 2^31. Every output is a pure function
+    of the arguments.
+
+    done (uint8 [B], updated in place) with 0 <= eos_id < V: a set flag gives
+    n_accept 0, next_token eos_id and accept_prob 0, nothing drawn; otherwise
+    done[b] |= next_token == eos_id. `details`, a list, receives per row t a
+    dict of the fp64 arrays the tests' preconditions need (p, q, a_p, a_q, g,
+    u, px, qx, the sanitised x, T, and cand, the row's candidate token)."""
+    import numpy as np
+    if p_logits.dim() != 3 or q_logits.dim() != 3 \
+            or p_logits.shape[1] < 2 or p_logits.shape[2] < 1 \
+            or tuple(q_logits.shape) != (p_logits.shape[0],
+                                         p_logits.shape[1] - 1,
+                                         p_logits.shape[2]):
+        raise ValueError("need p_logits [B, k+1, V] and q_logits [B, k, V] "
+                         f"with k, V >= 1, got {tuple(p_logits.shape)} and "
+                         f"{tuple(q_logits.shape)}")
+    B, k1, V = p_logits.shape
+    k = k1 - 1
+    if tuple(draft_tokens.shape) != (B, k):
+        raise ValueError(f"draft_tokens must be [B, k] = [{B}, {k}], got "
+                         f"{tuple(draft_tokens.shape)}")
+    if not (0.0 <= float(temperature) < 1e30):
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    if B * k1 >= 2 ** 31:
+        raise ValueError(f"B (k + 1) must be below 2^31, got {B * k1}")
+    if done is not None and not 0 <= int(eos_id) < V:
+        raise ValueError(f"with done, eos_id must be in [0, {V}), got "
+                         f"{eos_id}")
+    dev = p_logits.device
+
+    def keys(t):
+        return sample_keys(t.detach().to(device="cpu", dtype=torch.bfloat16)
+                           .contiguous().view(torch.int16).numpy()
+                           .view(np.uint16))
+    kp, kq = keys(p_logits), keys(q_logits)
+    x = draft_tokens.detach().to("cpu").numpy().astype(np.int64)
+    greedy = float(temperature) == 0.0
+    T = 1.0 if greedy else float(np.float32(temperature))
+    rows_b = np.arange(B)
+    accept = np.zeros((B, k), dtype=bool)
+    aprob = np.zeros((B, k), dtype=np.float64)
+    cand = np.zeros((B, k1), dtype=np.int64)
+    for t in range(k1):
+        if greedy:
+            cand[:, t] = kp[:, t].argmax(axis=1)      # lowest index on ties
+            if t < k:
+                accept[:, t] = x[:, t] == cand[:, t]
+                aprob[:, t] = accept[:, t]
+            continue
+        p, a_p, xp = _spec_softmax(kp[:, t], T)
+        word1 = (SPEC_ROW_TAG | (rows_b * k1 + t))[:, None]
+        g = -np.log(-np.log(_spec_uniform(np.arange(V)[None, :], word1, step,
+                                          seed)))
+        score = np.where(kp[:, t] > 0, xp / T + g, -np.inf)
+        cand[:, t] = score.argmax(axis=1)             # the draw from p_t
+        det = dict(p=p, a_p=a_p, g=g, x=xp, T=T)
+        if t < k:
+            q, a_q, _ = _spec_softmax(kq[:, t], T)
+            ok = (x[:, t] >= 0) & (x[:, t] < V)
+            xc = np.clip(x[:, t], 0, V - 1)
+            px = np.where(ok, p[rows_b, xc], 0.0)
+            qx = np.where(ok, q[rows_b, xc], 0.0)
+            u = _spec_uniform(SPEC_ACCEPT_WORD, word1[:, 0], step, seed)
+            accept[:, t] = u * qx < px
+            aprob[:, t] = np.where(px >= qx, px > 0,
+                                   px / np.where(qx > 0, qx, 1.0))
+            r = p - q
+            pos = r > 0
+            res = np.where(pos, np.log(np.where(pos, r, 1.0)) + g, -np.inf)
+            cand[:, t] = np.where(pos.any(axis=1), res.argmax(axis=1),
+                                  cand[:, t])
+            det.update(q=q, a_q=a_q, u=u, px=px, qx=qx)
+        if details is not None:
+            det["cand"] = cand[:, t].copy()
+            details.append(det)
+    n_accept = np.cumprod(accept, axis=1).sum(axis=1).astype(np.int32)
+    next_token = cand[rows_b, n_accept]
+    if done is not None:
+        done_np = done.detach().to("cpu").numpy()      # shared when on CPU
+        fin = done_np != 0
+        n_accept[fin] = 0
+        next_token[fin] = int(eos_id)
+        aprob[fin] = 0.0
+        done_np[:] = fin | (next_token == int(eos_id))
+        if done.device.type != "cpu":
+            done.copy_(torch.from_numpy(done_np))
+    return (torch.from_numpy(n_accept).to(dev),
+            torch.from_numpy(next_token).to(dev),
+            torch.from_numpy(aprob.astype(np.float32)).to(dev))
+
+
 def causal_lm_loss(logits: torch.Tensor, labels: torch.Tensor,
                    ignore_index: int = -100) -> torch.Tensor:
     """Shifted causal-LM cross entropy (HF CausalLM loss inside K1/K9)."""

@@ -17,7 +17,11 @@ models.quantize_weights(model): every linear as e4m3 codes with one scale per
 output row, half the weight bytes per token (any of the paths above; the HIP
 kernel serves a bf16 model on the GPU). --weight-dtype fp4 does the same in
 OCP MXFP4: e2m1 codes with one power-of-two scale per 32 weights, about 0.53
-bytes per weight. Beyond the reference's surface (it has no
+bytes per weight. --draft-weight-dtype {fp8,fp4} --spec-k K (implies
+--device-sampling; not with --top-k / --top-p) decodes speculatively with a
+quantised copy of the checkpoint as its own draft: K drafted tokens per
+round, checked by one forward of the model and ops.spec_verify. Beyond the
+reference's surface (it has no
 generation path); useful for judging what a checkpoint learned.
 
 Usage (config overrides use the same syntax as main.py):
@@ -130,6 +134,13 @@ def main(argv=None) -> str:
                          "--device-sampling)")
     ap.add_argument("--top-p", type=float, default=1.0,
                     help="nucleus mass (>= 1 = off; needs --device-sampling)")
+    ap.add_argument("--draft-weight-dtype", choices=("fp8", "fp4"),
+                    default=None,
+                    help="speculative decoding with a quantised copy of the "
+                         "checkpoint as the draft (implies "
+                         "--device-sampling; not with --top-k / --top-p)")
+    ap.add_argument("--spec-k", type=int, default=4,
+                    help="drafted tokens per round with --draft-weight-dtype")
     ap.add_argument("overrides", nargs="*",
                     help="config overrides, e.g. model=gptneo")
     args = ap.parse_args(argv)
@@ -137,6 +148,13 @@ def main(argv=None) -> str:
         ap.error("need --prefill-chunk >= 0")
     if args.top_k < 0 or not args.top_p > 0:
         ap.error("need --top-k >= 0 and --top-p > 0")
+    if args.draft_weight_dtype is not None:
+        if args.top_k != 0 or args.top_p < 1.0:
+            ap.error("--draft-weight-dtype does not combine with --top-k / "
+                     "--top-p")
+        if args.spec_k < 1:
+            ap.error("need --spec-k >= 1")
+        args.device_sampling = True
     if (args.top_k != 0 or args.top_p < 1.0) and not args.device_sampling:
         ap.error("--top-k / --top-p need --device-sampling")
 
@@ -152,11 +170,14 @@ def main(argv=None) -> str:
                         vocab_size_override=tok.get_vocab_size())
     load_pretrained(model, args.ckpt)
     model = model.to(device)
+    codes = {"fp8": torch.float8_e4m3fn, "fp4": torch.float4_e2m1fn_x2}
+    draft = None
+    if args.draft_weight_dtype is not None:
+        from acco_amd.models import quantize_weights
+        draft = quantize_weights(model.eval(), codes[args.draft_weight_dtype])
     if args.weight_dtype != "bf16":
         from acco_amd.models import quantize_weights
-        model = quantize_weights(
-            model.eval(), torch.float8_e4m3fn if args.weight_dtype == "fp8"
-            else torch.float4_e2m1fn_x2)
+        model = quantize_weights(model.eval(), codes[args.weight_dtype])
 
     ids = torch.tensor([tok.encode(args.prompt).ids], device=device)
     kv_dtype = torch.float8_e4m3fn if args.kv_dtype == "fp8" else None
@@ -169,7 +190,8 @@ def main(argv=None) -> str:
             model, ids, max_new=max(args.max_new, 0),
             temperature=max(args.temperature, 0.0), top_k=args.top_k,
             top_p=args.top_p, seed=args.seed,
-            prefill_chunk=args.prefill_chunk, kv_dtype=kv_dtype)
+            prefill_chunk=args.prefill_chunk, kv_dtype=kv_dtype,
+            draft=draft, spec_k=args.spec_k)
         out = out[:, :ids.shape[1] + int(n_new[0])]
     else:
         out = generate(model, ids, args.max_new, args.temperature, max_len,
