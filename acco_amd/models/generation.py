@@ -53,6 +53,10 @@ def generate(model, input_ids: torch.Tensor,
     (quantize_weights(model, dtype), ops.linear_w4): e2m1 codes with one
     power-of-two scale per 32 weights, about 0.53 bytes per weight; a model
     that already holds quantised linears of either kind is used as it is.
+    Calls of more than 64 rows (the prefill, prefill_chunk slices, a
+    speculative round of a large batch) run ops.gemm_w8 / ops.gemm_w4, HIP
+    kernels that read the codes as codes, up to ops.W8_GEMM_MAX_ROWS /
+    ops.W4_GEMM_MAX_ROWS rows.
     draft: a model of the same interface and vocab_size (for one,
     quantize_weights(model, torch.float4_e2m1fn_x2) of `model` itself) turns
     on speculative decoding, spec_k >= 1 drafted tokens per round

@@ -2,11 +2,14 @@
 stored as one-byte codes with one fp32 scale per output row
 (torch_ref.weight_quantize), half the weight bytes a decode step streams and
 half the weight memory of a model that is only generated from. Activations
-stay bf16; `ops.linear_w8` is the product. Nothing here trains.
+stay bf16; `ops.linear_w8` is the product for up to 64 rows of activations
+(decode) and `ops.gemm_w8` for more (prefill, long extends, batched
+speculative rounds), both HIP kernels that read the codes as codes. Nothing
+here trains.
 
-The same in OCP MXFP4 (`W4Linear`, `ops.linear_w4`): e2m1 codes with one
-power-of-two scale per 32 weights (torch_ref.weight_quantize_mxfp4), about
-0.53 bytes per weight."""
+The same in OCP MXFP4 (`W4Linear`, `ops.linear_w4` / `ops.gemm_w4`): e2m1
+codes with one power-of-two scale per 32 weights
+(torch_ref.weight_quantize_mxfp4), about 0.53 bytes per weight."""
 
 from __future__ import annotations
 
@@ -49,6 +52,17 @@ class _QuantLinear(nn.Module):
             setattr(self, name, getattr(self, name).to(dtype))
         return self
 
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """Routed by the rows of x over `_OPS` = (skinny, tiled, cap): up to
+        64 rows ops.`skinny`, more ops.`tiled` up to its measured cap
+        ops.`cap` (None: none), past that ops.`skinny` again, whose M > 64
+        path dequantises to a temporary."""
+        skinny, tiled, cap = self._OPS
+        rows, cap = x.numel() // max(x.shape[-1], 1), getattr(ops, cap)
+        op = tiled if rows > 64 and (cap is None or rows <= cap) else skinny
+        return getattr(ops, op)(x, self.codes, getattr(self, self._SCALE),
+                                self.bias)
+
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features="
                 f"{self.out_features}, bias={self.bias is not None}")
@@ -56,33 +70,31 @@ class _QuantLinear(nn.Module):
 
 class W8Linear(_QuantLinear):
     """A linear whose weight is e4m3 `codes` [out, in] and fp32 `scale` [out]
-    (buffers, as is the optional `bias`): forward is ops.linear_w8."""
+    (buffers, as is the optional `bias`): forward is ops.linear_w8 up to 64
+    rows of x and ops.gemm_w8 beyond."""
 
     _SCALE, _DTYPES = "scale", (torch.float8_e4m3fn, torch.float32)
+    _OPS = ("linear_w8", "gemm_w8", "W8_GEMM_MAX_ROWS")
     _quantize = staticmethod(ops.torch_ref.weight_quantize)
 
     def __init__(self, codes, scale, bias=None):
         super().__init__(codes, scale, bias)
         self.out_features, self.in_features = codes.shape
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return ops.linear_w8(x, self.codes, self.scale, self.bias)
-
 
 class W4Linear(_QuantLinear):
     """A linear whose weight is MXFP4: uint8 `codes` [out, in / 2] and uint8
     `scales` [out, in / 32] (buffers, as is the optional `bias`): forward is
-    ops.linear_w4. in_features must be a multiple of 32."""
+    ops.linear_w4 up to 64 rows of x and ops.gemm_w4 beyond. in_features must
+    be a multiple of 32."""
 
     _SCALE, _DTYPES = "scales", (torch.uint8, torch.uint8)
+    _OPS = ("linear_w4", "gemm_w4", "W4_GEMM_MAX_ROWS")
     _quantize = staticmethod(ops.torch_ref.weight_quantize_mxfp4)
 
     def __init__(self, codes, scales, bias=None):
         super().__init__(codes, scales, bias)
         self.out_features, self.in_features = codes.shape[0], 2 * codes.shape[1]
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return ops.linear_w4(x, self.codes, self.scales, self.bias)
 
 
 FP4 = torch.float4_e2m1fn_x2

@@ -473,6 +473,74 @@ def linear_w4_splits(m: int, n: int, k: int) -> Tuple[int, int]:
     return int(n_split), int(k_chunk)
 
 
+# The most rows W8Linear / W4Linear send to gemm_w8 / gemm_w4 (more go to
+# linear_w8 / linear_w4 and their M > 64 fallback); None: no cap. Set by
+# benchmarks/gemm_wq_micro.py: RESULTS.md, "Tiled quantised GEMMs". At 4096
+# rows gemm_w8 loses to dequantise + matmul at five of the seven shapes.
+W8_GEMM_MAX_ROWS: Optional[int] = 2048
+W4_GEMM_MAX_ROWS: Optional[int] = None
+
+
+def _gemm_wq(op, x, weight, bias, code_dtype, k_mult):
+    """gemm_w8 / gemm_w4 (`op`) on weight = (codes, scale(s)): torch_ref's
+    linear of the format outside the kernel's dtypes and K, else the
+    extension's `op` on x re-strided to its contract."""
+    K, N = x.shape[-1], weight[0].shape[0]
+    if (_use_ref(x) or x.dtype != torch.bfloat16
+            or weight[0].dtype != code_dtype or K % k_mult != 0 or K == 0):
+        return getattr(torch_ref, op.replace("gemm", "linear"))(x, *weight,
+                                                                bias)
+    x2 = x.reshape(-1, K)
+    if x2.shape[0] == 0:
+        return x.new_empty(*x.shape[:-1], N)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    return getattr(hip_ext(), op)(x2, *weight, bias).view(*x.shape[:-1], N)
+
+
+def gemm_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
+            bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_w8's product for any number of rows: y [..., N] = (x [..., K] @
+    float(codes)^T) * scale (+ bias), the leading dims of x flattened to M.
+
+    On the GPU, bf16 x, e4m3 codes and K % 64 == 0 run the tiled HIP kernel
+    (gemm_w8.hip) for every M >= 1: the codes are read as codes and converted
+    on the way to the MFMA, nothing of size N·K is written, exact products,
+    fp32 accumulation, one rounding to bf16. x may be a strided view with a
+    contiguous last dim. CPU tensors, other dtypes, other K and
+    ACCO_FORCE_REF=1 run torch_ref.linear_w8."""
+    return _gemm_wq("gemm_w8", x, (codes, scale), bias, FP8, 64)
+
+
+def gemm_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+            bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """linear_w4's product for any number of rows: y [..., N] = x [..., K] @
+    dequant(codes, scales)^T (+ bias), the leading dims of x flattened to M.
+
+    On the GPU, bf16 x and K % 128 == 0 run the tiled HIP kernel
+    (gemm_w4.hip) for every M >= 1: the 4-bit codes are read as codes, the
+    hardware convert applies the block scale on the way to the MFMA, nothing
+    of size N·K is written, fp32 accumulation, one rounding to bf16. CPU
+    tensors, other dtypes, other K and ACCO_FORCE_REF=1 run
+    torch_ref.linear_w4."""
+    return _gemm_wq("gemm_w4", x, (codes, scales), bias, torch.uint8, 128)
+
+
+def gemm_w8_tiles(m: int, n: int, k: int) -> Tuple[int, int, int, int]:
+    """(m_blocks, n_blocks, n_split, k_chunk) of the HIP gemm_w8 for M rows of
+    x, N output rows and K columns: m_blocks x n_blocks tiles, each over
+    n_split workgroups, workgroup i owning the columns [i·k_chunk,
+    (i+1)·k_chunk). A host function of its three arguments only."""
+    return tuple(int(v) for v in hip_ext().gemm_w8_grid(int(m), int(n),
+                                                        int(k)))
+
+
+def gemm_w4_tiles(m: int, n: int, k: int) -> Tuple[int, int, int, int]:
+    """gemm_w8_tiles for the HIP gemm_w4."""
+    return tuple(int(v) for v in hip_ext().gemm_w4_grid(int(m), int(n),
+                                                        int(k)))
+
+
 def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int, step: int,
                   done: Optional[torch.Tensor] = None, eos_id: int = -1

@@ -1463,6 +1463,105 @@ at::Tensor linear_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
   });
 }
 
+// ---- tiled weight-only GEMMs (gemm_w8.hip, gemm_w4.hip): the two linears
+// above for any M >= 1
+using gemm_wq_grid_fn = void (*)(int, int, int, int*, int*, int*, int*);
+
+// (m_blocks, n_blocks, n_split, k_chunk) of a GEMM for its three sizes
+static std::vector<int64_t> gemm_wq_grid(const char* op, gemm_wq_grid_fn grid,
+                                         int64_t k_mult, int64_t M, int64_t N,
+                                         int64_t K) {
+  TORCH_CHECK(M >= 1 && N >= 1 && N < (1LL << 24) && K >= k_mult &&
+              K < (1LL << 24) && K % k_mult == 0 && M * N < (1LL << 31),
+              op, ": need M >= 1, 1 <= N < 2^24, M * N < 2^31 and K < 2^24 a "
+              "positive multiple of ", k_mult, ", got M=", M, " N=", N, " K=",
+              K);
+  int mb, nb, n_split, k_chunk;
+  grid((int)M, (int)N, (int)K, &mb, &nb, &n_split, &k_chunk);
+  TORCH_CHECK((int64_t)mb * nb * n_split < (1LL << 31), op,
+              ": too many workgroups for M=", M, " N=", N);
+  return {mb, nb, n_split, k_chunk};
+}
+
+std::vector<int64_t> gemm_w8_grid(int64_t M, int64_t N, int64_t K) {
+  return gemm_wq_grid("gemm_w8", acco_gemm_w8_grid, 64, M, N, K);
+}
+
+std::vector<int64_t> gemm_w4_grid(int64_t M, int64_t N, int64_t K) {
+  return gemm_wq_grid("gemm_w4", acco_gemm_w4_grid, 128, M, N, K);
+}
+
+// y and the partials' workspace for the grid's n_split, then launch(y,
+// workspace) and the launch check
+template <class Launch>
+static at::Tensor gemm_wq_run(int64_t n_split, const at::Tensor& x, int64_t N,
+                              Launch launch) {
+  const int64_t M = x.size(0);
+  auto y = at::empty({M, N}, x.options());
+  auto ws = at::empty({n_split > 1 ? n_split * M * N : 0},
+                      x.options().dtype(at::kFloat));
+  launch(y.data_ptr(), ws.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return y;
+}
+
+// The argument contract of linear_w8 with any M >= 1 (gemm_wq_grid has the
+// sizes)
+at::Tensor gemm_w8(at::Tensor x, at::Tensor codes, at::Tensor scale,
+                   c10::optional<at::Tensor> bias) {
+  check_skinny_x(x);
+  TORCH_CHECK(codes.is_cuda() && codes.device() == x.device() &&
+              codes.scalar_type() == at::kFloat8_e4m3fn &&
+              codes.is_contiguous() && codes.dim() == 2 &&
+              codes.size(1) == x.size(1),
+              "codes must be contiguous float8_e4m3fn [N, K = ", x.size(1),
+              "] on ", x.device(), ", got ", codes.scalar_type(), " ",
+              codes.sizes(), " on ", codes.device());
+  const int64_t M = x.size(0), K = x.size(1), N = codes.size(0);
+  const int64_t n_split = gemm_w8_grid(M, N, K)[2];
+  TORCH_CHECK(aligned_to(x, 16) && aligned_to(codes, 16),
+              "x and codes must be 16-byte aligned");
+  check_f32_vec(scale, N, x, "scale");
+  TORCH_CHECK(scale.dim() == 1, "scale must be [N], got ", scale.sizes());
+  const int64_t rs = check_skinny_x_bias(x, N, bias);
+  return gemm_wq_run(n_split, x, N, [&](void* y, float* ws) {
+    acco_gemm_w8(x.data_ptr(), codes.data_ptr(), scale.data_ptr<float>(),
+                 bias.has_value() ? bias->data_ptr() : nullptr, y, ws, (int)M,
+                 (int)N, (int)K, rs, cur_stream());
+  });
+}
+
+// The argument contract of linear_w4 with any M >= 1; the scales need no
+// alignment here (the kernel loads them a byte at a time)
+at::Tensor gemm_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
+                   c10::optional<at::Tensor> bias) {
+  check_skinny_x(x);
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(codes.is_cuda() && codes.device() == x.device() &&
+              codes.scalar_type() == at::kByte && codes.is_contiguous() &&
+              codes.dim() == 2 && codes.size(1) * 2 == K,
+              "codes must be contiguous uint8 [N, K / 2 = ", K / 2, "] on ",
+              x.device(), ", got ", codes.scalar_type(), " ", codes.sizes(),
+              " on ", codes.device());
+  const int64_t N = codes.size(0);
+  const int64_t n_split = gemm_w4_grid(M, N, K)[2];
+  TORCH_CHECK(scales.is_cuda() && scales.device() == x.device() &&
+              scales.scalar_type() == at::kByte && scales.is_contiguous() &&
+              scales.dim() == 2 && scales.size(0) == N &&
+              scales.size(1) * 32 == K,
+              "scales must be contiguous uint8 [N, K / 32] = [", N, ", ",
+              K / 32, "] on ", x.device(), ", got ", scales.scalar_type(), " ",
+              scales.sizes(), " on ", scales.device());
+  TORCH_CHECK(aligned_to(x, 16) && aligned_to(codes, 16),
+              "x and codes must be 16-byte aligned");
+  const int64_t rs = check_skinny_x_bias(x, N, bias);
+  return gemm_wq_run(n_split, x, N, [&](void* y, float* ws) {
+    acco_gemm_w4(x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+                 bias.has_value() ? bias->data_ptr() : nullptr, y, ws, (int)M,
+                 (int)N, (int)K, rs, cur_stream());
+  });
+}
+
 // ---- on-device sampling (sample.hip)
 // (token int64 [B], logprob fp32 [B], thr bf16 [B], n_kept int32 [B]) of one
 // draw per row. The argument contract: logits CUDA bf16 [B, V] whose last dim
@@ -1655,6 +1754,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_w4_grid", &linear_w4_grid, py::arg("M"), py::arg("N"),
         py::arg("K"));
   m.def("linear_w4", &linear_w4, py::arg("x"), py::arg("codes"),
+        py::arg("scales"), py::arg("bias"));
+  m.def("gemm_w8_grid", &gemm_w8_grid, py::arg("M"), py::arg("N"),
+        py::arg("K"));
+  m.def("gemm_w8", &gemm_w8, py::arg("x"), py::arg("codes"),
+        py::arg("scale"), py::arg("bias"));
+  m.def("gemm_w4_grid", &gemm_w4_grid, py::arg("M"), py::arg("N"),
+        py::arg("K"));
+  m.def("gemm_w4", &gemm_w4, py::arg("x"), py::arg("codes"),
         py::arg("scales"), py::arg("bias"));
   m.def("fused_adamw", &fused_adamw,
         "Fused sharded AdamW (gfx950): cast+scale+AdamW+bf16 writeout; "

@@ -169,6 +169,24 @@ void acco_linear_w4(const void* x, const void* codes, const void* scales,
                     const void* bias, void* y, float* workspace, int M, int N,
                     int K, long long x_rs, hipStream_t stream);
 
+// ---- gemm_w8.hip, gemm_w4.hip
+// The same two products for any M >= 1 (arguments as acco_linear_w8 /
+// acco_linear_w4; M * N and the workgroup count below 2^31). m_blocks blocks
+// of 64 rows of x by n_blocks blocks of 256 weight rows, each over n_split
+// workgroups of k_chunk columns (host only, a function of the three sizes);
+// workspace: n_split * M * N fp32 when n_split > 1 (written before it is
+// read), unused otherwise.
+void acco_gemm_w8_grid(int M, int N, int K, int* m_blocks, int* n_blocks,
+                       int* n_split, int* k_chunk);
+void acco_gemm_w8(const void* x, const void* codes, const float* scale,
+                  const void* bias, void* y, float* workspace, int M, int N,
+                  int K, long long x_rs, hipStream_t stream);
+void acco_gemm_w4_grid(int M, int N, int K, int* m_blocks, int* n_blocks,
+                       int* n_split, int* k_chunk);
+void acco_gemm_w4(const void* x, const void* codes, const void* scales,
+                  const void* bias, void* y, float* workspace, int M, int N,
+                  int K, long long x_rs, hipStream_t stream);
+
 // ---- ce.hip
 // bf16 logits on a 16-byte aligned base (any V). A token is valid iff
 // 0 <= target < V; any other target (-100, >= V) is ignored: lse 0, no loss,

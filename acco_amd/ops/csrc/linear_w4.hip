@@ -65,6 +65,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "linear_skinny.h"
+#include "quant_formats.h"
 
 namespace {
 
@@ -79,30 +80,8 @@ struct Frag {
   unsigned s[kTiles];
 };
 
-// 8 codes (one dword, k ascending from the low nibble) times 2^(s - 127) ->
-// 8 bf16, the B fragment of one MFMA; `scale` is s << 23 read as fp32
-ACCO_DEV short8 codes_to_bf16(unsigned dw, float scale) {
-  union { decltype(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(0u, 1.f, 0)) v;
-          unsigned u; } p[4];
-  p[0].v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 0);
-  p[1].v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 1);
-  p[2].v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 2);
-  p[3].v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(dw, scale, 3);
-  short8 out;
-  unsigned* o = reinterpret_cast<unsigned*>(&out);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) o[i] = p[i].u;
-  return out;
-}
-
-// the one place a finished dot product becomes an output element
-struct Finish {
-  const u16* bias;
-  ACCO_DEV u16 operator()(float dot, int n) const {
-    const float b = bias != nullptr ? bf16_to_f32(bias[n]) : 0.f;
-    return f32_to_bf16(dot + b);
-  }
-};
+using mxfp4::codes_to_bf16;            // quant_formats.h
+using mxfp4::Finish;
 
 template <int MT>
 __global__ __launch_bounds__(kThreads)

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "linear_skinny.h"
+#include "quant_formats.h"
 
 namespace {
 
@@ -39,40 +40,8 @@ using namespace skinny;
 
 constexpr int kStep = 64;                       // k per 16-byte load of a tile
 
-// 16 e4m3 codes -> 16 bf16, the B fragments of the two MFMAs of a step. An
-// e4m3 value has four significant bits, so the high half of its fp32 is the
-// value itself in bf16.
-ACCO_DEV void codes_to_bf16(const uint4& raw, short8& lo, short8& hi) {
-  const int* w = reinterpret_cast<const int*>(&raw);
-  unsigned out[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
-    const auto b = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
-    // v_perm_b32: the high halves of two dwords, the first in the low half
-    out[2 * i] = __builtin_amdgcn_perm(__float_as_uint(a[1]),
-                                       __float_as_uint(a[0]), 0x07060302u);
-    out[2 * i + 1] = __builtin_amdgcn_perm(__float_as_uint(b[1]),
-                                           __float_as_uint(b[0]), 0x07060302u);
-  }
-  unsigned* l = reinterpret_cast<unsigned*>(&lo);
-  unsigned* h = reinterpret_cast<unsigned*>(&hi);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    l[i] = out[i];
-    h[i] = out[4 + i];
-  }
-}
-
-// the one place a finished dot product becomes an output element
-struct Finish {
-  const float* scale;
-  const u16* bias;
-  ACCO_DEV u16 operator()(float dot, int n) const {
-    const float b = bias != nullptr ? bf16_to_f32(bias[n]) : 0.f;
-    return f32_to_bf16(__fmaf_rn(dot, scale[n], b));
-  }
-};
+using e4m3::codes_to_bf16;             // quant_formats.h
+using e4m3::Finish;
 
 template <int MT>
 __global__ __launch_bounds__(kThreads)
