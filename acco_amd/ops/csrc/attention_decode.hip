@@ -8,12 +8,12 @@
 // Memory-bound work, so the structure follows the bytes:
 //   - one workgroup serves all rep = H / Hkv query heads of one kv head, so
 //     each K / V row is read once;
-//   - D / 8 adjacent lanes own one key: each loads 16 bytes of the K row and
-//     16 bytes of the V row straight from global memory to registers (no LDS
-//     staging: every byte is used once), holds the matching 8 dims of all rep
-//     queries in registers, and the partial dots are summed over the D / 8
-//     lanes by xor shuffles; a wave covers 512 / D keys per step, two steps
-//     are in flight;
+//   - D / E adjacent lanes own one key, E = 8 dims per lane for a bf16 cache:
+//     each loads 16 bytes of the K row and 16 bytes of the V row straight
+//     from global memory to registers (no LDS staging: every byte is used
+//     once), holds the matching E dims of all rep queries in registers, and
+//     the partial dots are summed over the D / E lanes by xor shuffles; a
+//     wave covers 64 E / D keys per step, two steps are in flight;
 //   - fp32 scores in the log2 domain, online softmax per lane group, P stays
 //     fp32 (there is no second MFMA to round it for).
 // The key range is split across gridDim.x workgroups (flash-decoding): split
@@ -27,9 +27,25 @@
 // wave or split merges as weight exp2(kNegBig - m) = 0 (or 1 against another
 // empty one, times l = 0) and never as exp2(-inf - (-inf)). L = 0 gives o = 0.
 //
-// attn_decode_fp8_kernel is the same skeleton for an e4m3 cache (one-byte
-// codes and one fp32 scale per row): half the K / V bytes per key, so the
-// lanes regroup (its own comment below); both kernels end in decode_finish.
+// An e4m3 cache (acco_kv_append_fp8) holds codes of one byte, row value =
+// code * scale with k_scale / v_scale fp32 [B, Hkv, Smax]. The bytes halve,
+// so the lanes regroup: a 16-byte load holds E = 16 dims, D / 16 adjacent
+// lanes own one key and a wave covers 1024 / D keys per step. A lane then
+// holds 16 dims of q and of o per head, 32 * REP registers: up to REP = 3
+// that fits the 256 VGPRs, from REP = 4 it does not (the compiler parks the
+// rest in AGPRs and, at REP = 8, in scratch), so those group sizes take E = 8
+// dims per lane by 8-byte loads, the lane layout and register budget of the
+// bf16 cache. Each lane group also loads its key's two scales (one address in
+// all its lanes). The K scale multiplies the finished dot, s = (q . codes) *
+// (k_scale * scale_log2); the V scale is folded into p once per key, o +=
+// (p * v_scale) * code. No row at or beyond L is loaded, codes or scale.
+//
+// decode_body is the kernel for both caches; a Cache policy carries the
+// element and load types, E, the unpack and whether rows have scales. The two
+// __global__ wrappers differ in their build: attn_decode_fp8_kernel is built
+// without the packed fp32 VALU ops (see attention_extend.hip), while
+// attn_decode_kernel keeps the build it was measured with. The body is
+// force-inlined and takes its caller's target features.
 //
 // The split count is a guess that nobody has measured: about two workgroups
 // per CU (512) over B * Hkv, at least 256 keys per split, at most 64 splits.
@@ -40,10 +56,12 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "quant_formats.h"
 
 namespace {
 
 using u16 = unsigned short;
+using u8 = unsigned char;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
@@ -132,142 +150,43 @@ ACCO_DEV void decode_finish(float (&m)[REP], float (&l)[REP],
   }
 }
 
-// workspace layout, fp32: ml [B*H, n_split, 2] then o [B*H, n_split, D]
-template <int D, int REP>
-__global__ __launch_bounds__(kThreads)
-void attn_decode_kernel(const u16* __restrict__ q,
-                        const u16* __restrict__ k_cache,
-                        const u16* __restrict__ v_cache,
-                        const int* __restrict__ cache_len,
-                        float* __restrict__ part_ml,
-                        float* __restrict__ part_o, int Hkv, int Smax,
-                        int window, int chunk, float scale_log2,
-                        long long q_rs) {
-  constexpr int G = D / 8;            // lanes per key row
-  constexpr int NG = kThreads / G;    // key rows per block step
-  const int split = blockIdx.x, n_split = gridDim.x;
-  const int bk = blockIdx.y;          // b * Hkv + kv head
-  const int b = bk / Hkv, kvh = bk % Hkv;
-  const int tid = threadIdx.x;
-  const int g = tid / G, c8 = (tid % G) * 8;
+// What a cache format brings to decode_body: the element and 16- or 8-byte
+// load types of a row, E dims per lane, their widening to fp32, and whether
+// rows carry scales.
+struct Bf16Cache {
+  using Elem = u16;
+  using Raw = uint4;
+  static constexpr int E = 8;
+  static constexpr bool kScales = false;
+  static ACCO_DEV void unpack(const Raw& raw, float* f) { unpack8(raw, f); }
+};
 
-  const int L = min(max(cache_len[b], 0), Smax);
-  const int lo = window > 0 ? max(L - window, 0) : 0;
-  const long long c0 = (long long)split * chunk;
-  const int start = (int)max((long long)lo, min(c0, (long long)L));
-  const int end = (int)min((long long)L, c0 + chunk);
-
-  float qf[REP][8];
-  const u16* qp = q + (long long)b * q_rs + (long long)kvh * REP * D + c8;
-#pragma unroll
-  for (int h = 0; h < REP; ++h)
-    unpack8(*reinterpret_cast<const uint4*>(qp + h * D), qf[h]);
-
-  float m[REP], l[REP], o[REP][8];
-#pragma unroll
-  for (int h = 0; h < REP; ++h) {
-    m[h] = kNegBig;
-    l[h] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[h][i] = 0.f;
+template <int E_>
+struct Fp8Cache {
+  using Elem = u8;
+  using Raw = typename std::conditional<E_ == 16, uint4, uint2>::type;
+  static constexpr int E = E_;
+  static constexpr bool kScales = true;
+  static ACCO_DEV void unpack(const Raw& raw, float* f) {
+    e4m3::unpack_fp8<E>(raw, f);
   }
+};
 
-  const long long base = (long long)bk * Smax * D + c8;
-  auto step = [&](const uint4& kraw, const uint4& vraw) {
-    float kf[8], vf[8];
-    unpack8(kraw, kf);
-    unpack8(vraw, vf);
-#pragma unroll
-    for (int h = 0; h < REP; ++h) {
-      float a = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) a = __fmaf_rn(qf[h][i], kf[i], a);
-#pragma unroll
-      for (int off = G / 2; off > 0; off >>= 1) a += __shfl_xor(a, off);
-      const float s = a * scale_log2;
-      const float m_new = fmaxf(m[h], s);
-      const float alpha = exp2_fast(m[h] - m_new);
-      const float p = exp2_fast(s - m_new);
-      m[h] = m_new;
-      l[h] = __fmaf_rn(l[h], alpha, p);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        o[h][i] = __fmaf_rn(o[h][i], alpha, p * vf[i]);
-    }
-  };
-
-  // every j below satisfies start <= j < end <= L <= Smax
-  int j = start + g;
-  for (; j + NG < end; j += 2 * NG) {
-    const long long r0 = base + (long long)j * D;
-    const long long r1 = r0 + (long long)NG * D;
-    const uint4 k0 = *reinterpret_cast<const uint4*>(k_cache + r0);
-    const uint4 k1 = *reinterpret_cast<const uint4*>(k_cache + r1);
-    const uint4 v0 = *reinterpret_cast<const uint4*>(v_cache + r0);
-    const uint4 v1 = *reinterpret_cast<const uint4*>(v_cache + r1);
-    step(k0, v0);
-    step(k1, v1);
-  }
-  if (j < end) {
-    const long long r0 = base + (long long)j * D;
-    const uint4 k0 = *reinterpret_cast<const uint4*>(k_cache + r0);
-    const uint4 v0 = *reinterpret_cast<const uint4*>(v_cache + r0);
-    step(k0, v0);
-  }
-
-  decode_finish<D, REP, 8>(m, l, o, c8, bk, split, n_split, part_ml, part_o);
-}
-
-// This kernel's device code is built without the packed fp32 VALU ops (see
-// attention_extend.hip); the kernel above keeps the build it was measured
-// with. The host pass does not know the feature, hence the guard.
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma clang attribute push(                                      \
-    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
-#endif
-
-// E e4m3 codes (E / 4 dwords) -> fp32 by v_cvt_pk_f32_fp8, two values per
-// instruction
-template <int E, class Raw>
-ACCO_DEV void unpack_fp8(const Raw& raw, float* f) {
-  const int* w = reinterpret_cast<const int*>(&raw);
-#pragma unroll
-  for (int i = 0; i < E / 4; ++i) {
-    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
-    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
-    f[4 * i] = lo[0];
-    f[4 * i + 1] = lo[1];
-    f[4 * i + 2] = hi[0];
-    f[4 * i + 3] = hi[1];
-  }
-}
-
-// attn_decode_kernel for an e4m3 cache (acco_kv_append_fp8): codes of one
-// byte, row value = code * scale with k_scale / v_scale fp32 [B, Hkv, Smax].
-// The bytes halve, so the lanes regroup: a 16-byte load holds E = 16 dims,
-// D / 16 adjacent lanes own one key and a wave covers 1024 / D keys per step.
-// A lane then holds 16 dims of q and of o per head, 32 * REP registers: up to
-// REP = 3 that fits the 256 VGPRs, from REP = 4 it does not (the compiler
-// parks the rest in AGPRs and, at REP = 8, in scratch), so those group sizes
-// take E = 8 dims per lane by 8-byte loads, the lane layout and register
-// budget of the bf16 kernel. Each lane group also loads its key's two scales
-// (one address in all its lanes). The K scale multiplies the finished dot, s = (q . codes) * k_scale
-// * scale_log2; the V scale is folded into p once per key, o += (p * v_scale)
-// * code. Two steps in flight, the same online softmax, splits, workspace and
-// finish as above; no row at or beyond L is loaded, codes or scale.
-template <int D, int REP, int E = (REP <= 3 ? 16 : 8)>
-__global__ __launch_bounds__(kThreads)
-void attn_decode_fp8_kernel(const u16* __restrict__ q,
-                            const unsigned char* __restrict__ k_cache,
-                            const unsigned char* __restrict__ v_cache,
-                            const float* __restrict__ k_scale,
-                            const float* __restrict__ v_scale,
-                            const int* __restrict__ cache_len,
-                            float* __restrict__ part_ml,
-                            float* __restrict__ part_o, int Hkv, int Smax,
-                            int window, int chunk, float scale_log2,
-                            long long q_rs) {
-  using Raw = typename std::conditional<E == 16, uint4, uint2>::type;
+// workspace layout, fp32: ml [B*H, n_split, 2] then o [B*H, n_split, D].
+// k_scale / v_scale are read only if Cache::kScales.
+template <class Cache, int D, int REP>
+ACCO_DEV void decode_body(const u16* __restrict__ q,
+                          const typename Cache::Elem* __restrict__ k_cache,
+                          const typename Cache::Elem* __restrict__ v_cache,
+                          const float* __restrict__ k_scale,
+                          const float* __restrict__ v_scale,
+                          const int* __restrict__ cache_len,
+                          float* __restrict__ part_ml,
+                          float* __restrict__ part_o, int Hkv, int Smax,
+                          int window, int chunk, float scale_log2,
+                          long long q_rs) {
+  using Raw = typename Cache::Raw;
+  constexpr int E = Cache::E;
   constexpr int G = D / E;            // lanes per key row
   constexpr int NG = kThreads / G;    // key rows per block step
   const int split = blockIdx.x, n_split = gridDim.x;
@@ -299,13 +218,16 @@ void attn_decode_fp8_kernel(const u16* __restrict__ q,
     for (int i = 0; i < E; ++i) o[h][i] = 0.f;
   }
 
-  const long long srow = (long long)bk * Smax;    // first scale of the pair
+  const long long srow = (long long)bk * Smax;    // the pair's first row
   const long long base = srow * D + ce;
-  auto step = [&](const Raw& kraw, const Raw& vraw, float ks, float vs) {
+  // one key: ks and vs are its scales (unused without)
+  auto step = [&](const Raw& kraw, const Raw& vraw, float ks, float vs)
+                  __attribute__((always_inline)) {
     float kf[E], vf[E];
-    unpack_fp8<E>(kraw, kf);
-    unpack_fp8<E>(vraw, vf);
-    const float kss = ks * scale_log2;
+    Cache::unpack(kraw, kf);
+    Cache::unpack(vraw, vf);
+    float kss = scale_log2;
+    if constexpr (Cache::kScales) kss = ks * scale_log2;
 #pragma unroll
     for (int h = 0; h < REP; ++h) {
       float a = 0.f;
@@ -319,7 +241,8 @@ void attn_decode_fp8_kernel(const u16* __restrict__ q,
       const float p = exp2_fast(s - m_new);
       m[h] = m_new;
       l[h] = __fmaf_rn(l[h], alpha, p);
-      const float pv = p * vs;
+      float pv = p;
+      if constexpr (Cache::kScales) pv = p * vs;
 #pragma unroll
       for (int i = 0; i < E; ++i)
         o[h][i] = __fmaf_rn(o[h][i], alpha, pv * vf[i]);
@@ -335,8 +258,11 @@ void attn_decode_fp8_kernel(const u16* __restrict__ q,
     const Raw k1 = *reinterpret_cast<const Raw*>(k_cache + r1);
     const Raw v0 = *reinterpret_cast<const Raw*>(v_cache + r0);
     const Raw v1 = *reinterpret_cast<const Raw*>(v_cache + r1);
-    const float ks0 = k_scale[srow + j], ks1 = k_scale[srow + j + NG];
-    const float vs0 = v_scale[srow + j], vs1 = v_scale[srow + j + NG];
+    float ks0 = 0.f, ks1 = 0.f, vs0 = 0.f, vs1 = 0.f;
+    if constexpr (Cache::kScales) {
+      ks0 = k_scale[srow + j], ks1 = k_scale[srow + j + NG];
+      vs0 = v_scale[srow + j], vs1 = v_scale[srow + j + NG];
+    }
     step(k0, v0, ks0, vs0);
     step(k1, v1, ks1, vs1);
   }
@@ -344,10 +270,51 @@ void attn_decode_fp8_kernel(const u16* __restrict__ q,
     const long long r0 = base + (long long)j * D;
     const Raw k0 = *reinterpret_cast<const Raw*>(k_cache + r0);
     const Raw v0 = *reinterpret_cast<const Raw*>(v_cache + r0);
-    step(k0, v0, k_scale[srow + j], v_scale[srow + j]);
+    float ks0 = 0.f, vs0 = 0.f;
+    if constexpr (Cache::kScales)
+      ks0 = k_scale[srow + j], vs0 = v_scale[srow + j];
+    step(k0, v0, ks0, vs0);
   }
 
   decode_finish<D, REP, E>(m, l, o, ce, bk, split, n_split, part_ml, part_o);
+}
+
+template <int D, int REP>
+__global__ __launch_bounds__(kThreads)
+void attn_decode_kernel(const u16* __restrict__ q,
+                        const u16* __restrict__ k_cache,
+                        const u16* __restrict__ v_cache,
+                        const int* __restrict__ cache_len,
+                        float* __restrict__ part_ml,
+                        float* __restrict__ part_o, int Hkv, int Smax,
+                        int window, int chunk, float scale_log2,
+                        long long q_rs) {
+  decode_body<Bf16Cache, D, REP>(q, k_cache, v_cache, nullptr, nullptr,
+                                 cache_len, part_ml, part_o, Hkv, Smax,
+                                 window, chunk, scale_log2, q_rs);
+}
+
+// The host pass does not know the feature, hence the guard.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(                                      \
+    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+
+template <int D, int REP, int E = (REP <= 3 ? 16 : 8)>
+__global__ __launch_bounds__(kThreads)
+void attn_decode_fp8_kernel(const u16* __restrict__ q,
+                            const u8* __restrict__ k_cache,
+                            const u8* __restrict__ v_cache,
+                            const float* __restrict__ k_scale,
+                            const float* __restrict__ v_scale,
+                            const int* __restrict__ cache_len,
+                            float* __restrict__ part_ml,
+                            float* __restrict__ part_o, int Hkv, int Smax,
+                            int window, int chunk, float scale_log2,
+                            long long q_rs) {
+  decode_body<Fp8Cache<E>, D, REP>(q, k_cache, v_cache, k_scale, v_scale,
+                                   cache_len, part_ml, part_o, Hkv, Smax,
+                                   window, chunk, scale_log2, q_rs);
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -375,47 +342,6 @@ __global__ void attn_decode_combine_kernel(const float* __restrict__ part_ml,
   o[bh * D + d] = f32_to_bf16(l > 0.f ? acc / l : 0.f);
 }
 
-template <int D>
-void launch_decode(int rep, dim3 grid, hipStream_t stream, const u16* q,
-                   const u16* kc, const u16* vc, const int* len, float* ml,
-                   float* po, int Hkv, int Smax, int window, int chunk,
-                   float scale_log2, long long q_rs) {
-#define ACCO_DECODE_REP(R)                                                   \
-  case R:                                                                    \
-    hipLaunchKernelGGL((attn_decode_kernel<D, R>), grid, dim3(kThreads), 0,  \
-                       stream, q, kc, vc, len, ml, po, Hkv, Smax, window,    \
-                       chunk, scale_log2, q_rs);                             \
-    break;
-  switch (rep) {
-    ACCO_DECODE_REP(1) ACCO_DECODE_REP(2) ACCO_DECODE_REP(3)
-    ACCO_DECODE_REP(4) ACCO_DECODE_REP(5) ACCO_DECODE_REP(6)
-    ACCO_DECODE_REP(7) ACCO_DECODE_REP(8)
-    default: break;   // the binding admits 1 <= rep <= 8 only
-  }
-#undef ACCO_DECODE_REP
-}
-
-template <int D>
-void launch_decode_fp8(int rep, dim3 grid, hipStream_t stream, const u16* q,
-                       const unsigned char* kc, const unsigned char* vc,
-                       const float* ks, const float* vs, const int* len,
-                       float* ml, float* po, int Hkv, int Smax, int window,
-                       int chunk, float scale_log2, long long q_rs) {
-#define ACCO_DECODE_REP(R)                                                   \
-  case R:                                                                    \
-    hipLaunchKernelGGL((attn_decode_fp8_kernel<D, R>), grid,                 \
-                       dim3(kThreads), 0, stream, q, kc, vc, ks, vs, len,    \
-                       ml, po, Hkv, Smax, window, chunk, scale_log2, q_rs);  \
-    break;
-  switch (rep) {
-    ACCO_DECODE_REP(1) ACCO_DECODE_REP(2) ACCO_DECODE_REP(3)
-    ACCO_DECODE_REP(4) ACCO_DECODE_REP(5) ACCO_DECODE_REP(6)
-    ACCO_DECODE_REP(7) ACCO_DECODE_REP(8)
-    default: break;   // the binding admits 1 <= rep <= 8 only
-  }
-#undef ACCO_DECODE_REP
-}
-
 }  // namespace
 
 extern "C" void acco_attn_decode_grid(long long BHkv, int Smax, int* n_split,
@@ -432,27 +358,58 @@ extern "C" void acco_attn_decode_grid(long long BHkv, int Smax, int* n_split,
   *chunk = (int)c;
 }
 
-extern "C" void acco_attn_decode(const void* q, const void* k_cache,
-                                 const void* v_cache, const int* cache_len,
-                                 void* o, float* workspace, int B, int H,
-                                 int Hkv, int D, int Smax, float scale,
-                                 int window, long long q_rs,
-                                 hipStream_t stream) {
+namespace {
+
+// both entry points: k_scale == nullptr is the bf16 cache
+void launch_decode(const void* q, const void* k_cache, const void* v_cache,
+                   const float* k_scale, const float* v_scale,
+                   const int* cache_len, void* o, float* workspace, int B,
+                   int H, int Hkv, int D, int Smax, float scale, int window,
+                   long long q_rs, hipStream_t stream) {
   int n_split, chunk;
   acco_attn_decode_grid((long long)B * Hkv, Smax, &n_split, &chunk);
   float* ml = workspace;
   float* po = workspace + (long long)B * H * n_split * 2;
   const dim3 grid(n_split, B * Hkv);
   const float scale_log2 = scale * kLog2e;
-  if (D == 64)
-    launch_decode<64>(H / Hkv, grid, stream, (const u16*)q,
-                      (const u16*)k_cache, (const u16*)v_cache, cache_len, ml,
-                      po, Hkv, Smax, window, chunk, scale_log2, q_rs);
-  else
-    launch_decode<128>(H / Hkv, grid, stream, (const u16*)q,
-                       (const u16*)k_cache, (const u16*)v_cache, cache_len,
-                       ml, po, Hkv, Smax, window, chunk, scale_log2, q_rs);
+#define ACCO_DECODE_REP(DD, R)                                                \
+  case R:                                                                     \
+    if (k_scale == nullptr)                                                   \
+      hipLaunchKernelGGL((attn_decode_kernel<DD, R>), grid, dim3(kThreads),   \
+                         0, stream, (const u16*)q, (const u16*)k_cache,       \
+                         (const u16*)v_cache, cache_len, ml, po, Hkv, Smax,   \
+                         window, chunk, scale_log2, q_rs);                    \
+    else                                                                      \
+      hipLaunchKernelGGL((attn_decode_fp8_kernel<DD, R>), grid,               \
+                         dim3(kThreads), 0, stream, (const u16*)q,            \
+                         (const u8*)k_cache, (const u8*)v_cache, k_scale,     \
+                         v_scale, cache_len, ml, po, Hkv, Smax, window,       \
+                         chunk, scale_log2, q_rs);                            \
+    break;
+#define ACCO_DECODE(DD)                                                       \
+  switch (H / Hkv) {                                                          \
+    ACCO_DECODE_REP(DD, 1) ACCO_DECODE_REP(DD, 2) ACCO_DECODE_REP(DD, 3)      \
+    ACCO_DECODE_REP(DD, 4) ACCO_DECODE_REP(DD, 5) ACCO_DECODE_REP(DD, 6)      \
+    ACCO_DECODE_REP(DD, 7) ACCO_DECODE_REP(DD, 8)                             \
+    default: break;   /* the binding admits 1 <= rep <= 8 only */             \
+  }
+  if (D == 64) ACCO_DECODE(64)
+  else ACCO_DECODE(128)
+#undef ACCO_DECODE
+#undef ACCO_DECODE_REP
   acco_attn_split_combine(ml, po, o, (long long)B * H, n_split, D, stream);
+}
+
+}  // namespace
+
+extern "C" void acco_attn_decode(const void* q, const void* k_cache,
+                                 const void* v_cache, const int* cache_len,
+                                 void* o, float* workspace, int B, int H,
+                                 int Hkv, int D, int Smax, float scale,
+                                 int window, long long q_rs,
+                                 hipStream_t stream) {
+  launch_decode(q, k_cache, v_cache, nullptr, nullptr, cache_len, o,
+                workspace, B, H, Hkv, D, Smax, scale, window, q_rs, stream);
 }
 
 extern "C" void acco_attn_decode_fp8(const void* q, const void* k_cache,
@@ -463,23 +420,8 @@ extern "C" void acco_attn_decode_fp8(const void* q, const void* k_cache,
                                      float* workspace, int B, int H, int Hkv,
                                      int D, int Smax, float scale, int window,
                                      long long q_rs, hipStream_t stream) {
-  int n_split, chunk;
-  acco_attn_decode_grid((long long)B * Hkv, Smax, &n_split, &chunk);
-  float* ml = workspace;
-  float* po = workspace + (long long)B * H * n_split * 2;
-  const dim3 grid(n_split, B * Hkv);
-  const float scale_log2 = scale * kLog2e;
-  const auto* kc = (const unsigned char*)k_cache;
-  const auto* vc = (const unsigned char*)v_cache;
-  if (D == 64)
-    launch_decode_fp8<64>(H / Hkv, grid, stream, (const u16*)q, kc, vc,
-                          k_scale, v_scale, cache_len, ml, po, Hkv, Smax,
-                          window, chunk, scale_log2, q_rs);
-  else
-    launch_decode_fp8<128>(H / Hkv, grid, stream, (const u16*)q, kc, vc,
-                           k_scale, v_scale, cache_len, ml, po, Hkv, Smax,
-                           window, chunk, scale_log2, q_rs);
-  acco_attn_split_combine(ml, po, o, (long long)B * H, n_split, D, stream);
+  launch_decode(q, k_cache, v_cache, k_scale, v_scale, cache_len, o,
+                workspace, B, H, Hkv, D, Smax, scale, window, q_rs, stream);
 }
 
 extern "C" void acco_attn_split_combine(const float* part_ml,

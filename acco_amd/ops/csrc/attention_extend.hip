@@ -67,6 +67,7 @@
 #pragma clang attribute push(                                      \
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
+#include "quant_formats.h"   // inside the region, as its comment says
 namespace {
 
 using namespace attn;
@@ -113,9 +114,9 @@ ACCO_DEV void stage_transposed_edge(const u16* base, int row0, int row_max,
 
 // ---- staging of an e4m3 cache. Every e4m3 value is exactly a bf16 value, so
 // the tiles in LDS, and with them both products, stay bf16: a 16-byte load
-// holds 16 dims, v_cvt_pk_f32_fp8 widens them and the upper halves of the
-// floats are the 16 bf16 bit patterns. EDGE carries the rules of the two
-// helpers above: row index clamped to row_max, a row past it zero-filled.
+// holds 16 dims and e4m3::codes_to_bf16_shift (quant_formats.h) widens them to
+// the 16 bf16 bit patterns. EDGE carries the rules of the two helpers above:
+// row index clamped to row_max, a row past it zero-filled.
 using u8 = unsigned char;
 
 template <bool EDGE>
@@ -124,17 +125,8 @@ ACCO_DEV void load16_fp8(const u8* base, int row, int row_max, int D, int d0,
   uint4 x = *reinterpret_cast<const uint4*>(
       base + (long long)(EDGE ? min(row, row_max) : row) * D + d0);
   if (EDGE && row > row_max) x = make_uint4(0, 0, 0, 0);
-  const int* w = reinterpret_cast<const int*>(&x);
-  unsigned* o2 = reinterpret_cast<unsigned*>(out);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
-    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
-    o2[2 * i] = (__float_as_uint(lo[0]) >> 16) |
-                (__float_as_uint(lo[1]) & 0xffff0000u);
-    o2[2 * i + 1] = (__float_as_uint(hi[0]) >> 16) |
-                    (__float_as_uint(hi[1]) & 0xffff0000u);
-  }
+  short8* o = reinterpret_cast<short8*>(out);
+  e4m3::codes_to_bf16_shift(x, o[0], o[1]);
 }
 
 template <int D, bool EDGE>

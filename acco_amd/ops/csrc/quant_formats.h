@@ -1,9 +1,11 @@
-// What the weight-only kernels of one format share (linear_w8.hip and
-// gemm_w8.hip, linear_w4.hip and gemm_w4.hip): the convert of a register of
-// codes to the bf16 MFMA operand, and `finish`, the one place a finished dot
-// product becomes an output element. Included inside the no-packed-fp32-ops
-// region of those files (linear_skinny.h says why), so this header includes
-// nothing but common.h.
+// What the kernels that read one quantised format share: for e4m3 the widening
+// of codes to fp32 (the fp8 KV cache of attention_decode.hip) and to the bf16
+// MFMA operand (attention_extend.hip, linear_w8.hip, gemm_w8.hip), for MXFP4
+// the bf16 convert of linear_w4.hip and gemm_w4.hip; and `finish`, the one
+// place a finished dot product of a weight-only kernel becomes an output
+// element. v_cvt_pk_f32_fp8 is named here and nowhere else. Included inside
+// the no-packed-fp32-ops region of some of those files (linear_skinny.h says
+// why), so this header includes nothing but common.h.
 #pragma once
 
 #include "common.h"
@@ -11,6 +13,22 @@
 namespace e4m3 {
 
 using short8 = __attribute__((ext_vector_type(8))) short;
+
+// E e4m3 codes (E / 4 dwords) -> fp32 by v_cvt_pk_f32_fp8, two values per
+// instruction
+template <int E, class Raw>
+ACCO_DEV void unpack_fp8(const Raw& raw, float* f) {
+  const int* w = reinterpret_cast<const int*>(&raw);
+#pragma unroll
+  for (int i = 0; i < E / 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
+}
 
 // 16 e4m3 codes -> 16 bf16, the B fragments of two MFMAs. An e4m3 value has
 // four significant bits, so the high half of its fp32 is the value itself in
@@ -27,6 +45,29 @@ ACCO_DEV void codes_to_bf16(const uint4& raw, short8& lo, short8& hi) {
                                        __float_as_uint(a[0]), 0x07060302u);
     out[2 * i + 1] = __builtin_amdgcn_perm(__float_as_uint(b[1]),
                                            __float_as_uint(b[0]), 0x07060302u);
+  }
+  unsigned* l = reinterpret_cast<unsigned*>(&lo);
+  unsigned* h = reinterpret_cast<unsigned*>(&hi);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    l[i] = out[i];
+    h[i] = out[4 + i];
+  }
+}
+
+// The same by shift and mask, for the staging of attention_extend.hip: with
+// the v_perm_b32 form one of its kernels' register counts moved (RESULTS.md).
+ACCO_DEV void codes_to_bf16_shift(const uint4& raw, short8& lo, short8& hi) {
+  const int* w = reinterpret_cast<const int*>(&raw);
+  unsigned out[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false);
+    const auto b = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
+    out[2 * i] = (__float_as_uint(a[0]) >> 16) |
+                 (__float_as_uint(a[1]) & 0xffff0000u);
+    out[2 * i + 1] = (__float_as_uint(b[0]) >> 16) |
+                     (__float_as_uint(b[1]) & 0xffff0000u);
   }
   unsigned* l = reinterpret_cast<unsigned*>(&lo);
   unsigned* h = reinterpret_cast<unsigned*>(&hi);

@@ -2,12 +2,9 @@
 // Gumbel-max draw per row of bf16 logits, so a generation loop never copies
 // logits to the host. torch_ref.sample_logits is the executable definition.
 //
-// Values and keys. On load -0 becomes +0, +-inf the largest finite bf16 of
-// that sign, and NaN the lowest key (0), which no threshold admits. Every
-// other value maps to an order-preserving 16-bit key (sign bit flipped for
-// x >= 0, all bits flipped for x < 0), so finite values have keys in
-// [0x0080, 0xff7f]. top-k and top-p thresholds are keys: selection compares
-// integers and is exact.
+// Values become the order-preserving 16-bit keys of sampling_common.h (-0,
+// +-inf and NaN as defined there). top-k and top-p thresholds are keys:
+// selection compares integers and is exact.
 //
 // One 1024-thread workgroup per row; the row (256 KB at V = 128k) is re-read
 // from L2 by each pass:
@@ -34,101 +31,21 @@
 // (seed_lo, seed_hi). Only kept elements draw. The draw is a pure function of
 // (logits, T, top_k, top_p, seed, step, row).
 //
-// Alignment: nothing is asked of the base or the row stride. Each row is
-// split by its own address into a scalar head up to the first 16-byte
-// boundary, aligned 16-byte vectors and a scalar tail of < 8 elements.
+// Alignment: nothing is asked of the base or the row stride (for_each_elem).
 
-#include <cstdint>
-
-#include "common.h"
 #include "kernels.h"
+#include "sampling_common.h"
 
 namespace {
 
-using u16 = unsigned short;
-using u32 = unsigned int;
-using u64 = unsigned long long;
+using namespace sampling;
 
-constexpr int BLOCK = 1024;
-constexpr int NWAVE = BLOCK / 64;
 constexpr int BINS = 256;
 constexpr int HSTRIDE = BINS + 1;
 constexpr int CNT_COPIES = 32;    // uint32 view of the histogram buffer
 constexpr int MASS_COPIES = 16;   // uint64 view of the same bytes
 constexpr int HIST_U64 = MASS_COPIES * HSTRIDE;
 static_assert(CNT_COPIES * HSTRIDE <= 2 * HIST_U64, "count view fits");
-constexpr u32 kKeyMin = 0x0080u;  // key of the lowest finite bf16
-constexpr u32 kKeyZero = 0x8000u;
-
-typedef unsigned int w4_ __attribute__((ext_vector_type(4)));
-
-ACCO_DEV u32 load_key(u32 bits) {
-  bits &= 0xffffu;
-  const u32 mag = bits & 0x7fffu;
-  if (mag > 0x7f80u) return 0u;                      // NaN: below everything
-  if (mag == 0u) return kKeyZero;                    // -0 -> +0
-  if (mag == 0x7f80u) bits = (bits & 0x8000u) | 0x7f7fu;   // +-inf clamped
-  return (bits & 0x8000u) ? (~bits & 0xffffu) : (bits | 0x8000u);
-}
-
-ACCO_DEV u16 key_bits(u32 key) {
-  return (u16)((key & 0x8000u) ? (key ^ 0x8000u) : (~key & 0xffffu));
-}
-
-ACCO_DEV float key_value(u32 key) { return bf16_to_f32(key_bits(key)); }
-
-// f(bits, index) for every element of the row, each exactly once
-template <class F>
-ACCO_DEV void for_each_elem(const u16* __restrict__ row, int V, F&& f) {
-  const int tid = threadIdx.x;
-  int peel = (int)(((16u - (u32)((uintptr_t)row & 15u)) & 15u) >> 1);
-  if (peel > V) peel = V;
-  const int nvec = (V - peel) / 8;
-  const int tail = peel + nvec * 8;
-  if (tid < peel) f((u32)row[tid], tid);
-  const w4_* body = reinterpret_cast<const w4_*>(row + peel);
-  // one vector per thread and iteration: four loads in flight measured the
-  // same (the passes are bound by the CU's VALU, not by load latency)
-  for (int c = tid; c < nvec; c += BLOCK) {
-    const w4_ q = body[c];
-    const int base = peel + c * 8;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      f(q[k] & 0xffffu, base + 2 * k);
-      f(q[k] >> 16, base + 2 * k + 1);
-    }
-  }
-  if (tail + tid < V) f((u32)row[tail + tid], tail + tid);
-}
-
-// exp((x - max) / T) as fixed point; the same pure function of the element
-// in every pass. c2 = log2(e) / T, arg <= 0, so the result is <= mscale.
-ACCO_DEV u64 fixed_mass(u32 key, float vmax, float c2, float mscale) {
-  const float e = __builtin_amdgcn_exp2f((key_value(key) - vmax) * c2);
-  return (u64)(e * mscale);
-}
-
-ACCO_DEV u32 philox_word0(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    const u64 p0 = (u64)0xD2511F53u * c0;
-    const u64 p1 = (u64)0xCD9E8D57u * c2;
-    const u32 n0 = (u32)(p1 >> 32) ^ c1 ^ k0;
-    const u32 n2 = (u32)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (u32)p1;
-    c3 = (u32)p0;
-    c0 = n0;
-    c2 = n2;
-  }
-  return c0;
-}
-
-ACCO_DEV float gumbel(u32 word) {
-  // (2r + 1) · 2^-24 = (r + 0.5) · 2^-23, exact: 2r + 1 < 2^24
-  const float u = (float)(2u * (word >> 9) + 1u) * 5.9604644775390625e-08f;
-  return -logf(-logf(u));
-}
 
 // One histogram level. Elements with key >= min_key (and, at level 1, with
 // high byte hi_bin) add their weight (1, or their fixed-point mass) to the
@@ -190,18 +107,6 @@ ACCO_DEV u32 search_level(const u64* suf, u32* found, u64 target,
   above += suf[bin + 1];
   __syncthreads();
   return bin;
-}
-
-struct Best {
-  float score;
-  int idx;
-};
-
-ACCO_DEV void better(Best& a, float score, int idx) {
-  if (score > a.score || (score == a.score && idx < a.idx)) {
-    a.score = score;
-    a.idx = idx;
-  }
 }
 
 __global__ __launch_bounds__(BLOCK) void sample_kernel(
@@ -346,17 +251,9 @@ extern "C" void acco_sample_logits(const void* logits, long long row_stride,
                                    unsigned char* done, long long eos_id,
                                    long long* token, float* logprob,
                                    void* thr, int* n_kept, hipStream_t s) {
-  const bool greedy = temperature == 0.0f;
-  const float T = greedy ? 1.0f : temperature;
-  // log2(e) / T rounded once: the exponent of a mass is one product away
-  const float c2 = (float)(1.4426950408889634 / (double)T);
-  // V masses of at most 2^shift each sum below 2^62
-  int bits = 0;
-  while ((1ll << bits) < (long long)V) ++bits;
-  const int shift = 62 - bits < 40 ? 62 - bits : 40;
-  const float mscale = ldexpf(1.0f, shift);
+  const SamplingParams sp = sampling_params(temperature, V);
   hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(BLOCK), 0, s,
-                     (const u16*)logits, row_stride, V, T, c2, mscale, greedy,
-                     top_k, top_p, seed, step, done, eos_id, token, logprob,
-                     (u16*)thr, n_kept);
+                     (const u16*)logits, row_stride, V, sp.T, sp.c2, sp.mscale,
+                     sp.greedy, top_k, top_p, seed, step, done, eos_id, token,
+                     logprob, (u16*)thr, n_kept);
 }

@@ -38,13 +38,9 @@
 // (b, t) sits at word 0 = i < V, the accept test's u_t at word 0 = 2^32 - 1.
 //
 // Alignment: each row is split by its own address into a scalar head, aligned
-// 16-byte vectors and a scalar tail (sample.hip's for_each_elem). p_t and q_t
+// 16-byte vectors and a scalar tail (for_each_elem). p_t and q_t
 // have different alignments when V is odd, so pass 3 walks p_t that way and
 // reads q_t[i] by a 2-byte load per element.
-//
-// load_key, key_value, for_each_elem, philox_word0, gumbel and Best are copies
-// of sample.hip's: lifting them into a header was not shown to leave
-// sample.hip's code object bit-identical, so they are duplicated here.
 //
 // First guesses that nobody has measured against an alternative: 1024 threads
 // per workgroup; one workgroup per row, which leaves most CUs idle at small
@@ -59,95 +55,16 @@
     __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
 #endif
 
-#include <cstdint>
-
-#include "common.h"
 #include "kernels.h"
+#include "sampling_common.h"
 
 namespace {
 
-using u16 = unsigned short;
-using u32 = unsigned int;
-using u64 = unsigned long long;
+using namespace sampling;
 
-constexpr int BLOCK = 1024;
-constexpr int NWAVE = BLOCK / 64;
 constexpr u32 kRowTag = 0x80000000u;      // word 1: no sampler row has bit 31
 constexpr u32 kAcceptWord = 0xffffffffu;  // word 0 of u_t: no index reaches it
 constexpr int kNoIdx = 0x7fffffff;
-
-typedef unsigned int w4_ __attribute__((ext_vector_type(4)));
-
-ACCO_DEV u32 load_key(u32 bits) {
-  bits &= 0xffffu;
-  const u32 mag = bits & 0x7fffu;
-  if (mag > 0x7f80u) return 0u;                      // NaN: below everything
-  if (mag == 0u) return 0x8000u;                     // -0 -> +0
-  if (mag == 0x7f80u) bits = (bits & 0x8000u) | 0x7f7fu;   // +-inf clamped
-  return (bits & 0x8000u) ? (~bits & 0xffffu) : (bits | 0x8000u);
-}
-
-ACCO_DEV float key_value(u32 key) {
-  return bf16_to_f32(
-      (u16)((key & 0x8000u) ? (key ^ 0x8000u) : (~key & 0xffffu)));
-}
-
-// f(bits, index) for every element of the row, each exactly once
-template <class F>
-ACCO_DEV void for_each_elem(const u16* __restrict__ row, int V, F&& f) {
-  const int tid = threadIdx.x;
-  int peel = (int)(((16u - (u32)((uintptr_t)row & 15u)) & 15u) >> 1);
-  if (peel > V) peel = V;
-  const int nvec = (V - peel) / 8;
-  const int tail = peel + nvec * 8;
-  if (tid < peel) f((u32)row[tid], tid);
-  const w4_* body = reinterpret_cast<const w4_*>(row + peel);
-  for (int c = tid; c < nvec; c += BLOCK) {
-    const w4_ v = body[c];
-    const int base = peel + c * 8;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f(v[j] & 0xffffu, base + 2 * j);
-      f(v[j] >> 16, base + 2 * j + 1);
-    }
-  }
-  if (tail + tid < V) f((u32)row[tail + tid], tail + tid);
-}
-
-ACCO_DEV u32 philox_word0(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    const u64 p0 = (u64)0xD2511F53u * c0;
-    const u64 p1 = (u64)0xCD9E8D57u * c2;
-    const u32 n0 = (u32)(p1 >> 32) ^ c1 ^ k0;
-    const u32 n2 = (u32)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (u32)p1;
-    c3 = (u32)p0;
-    c0 = n0;
-    c2 = n2;
-  }
-  return c0;
-}
-
-// (2r + 1) · 2^-24 = (r + 0.5) · 2^-23, exact: 2r + 1 < 2^24
-ACCO_DEV float uniform01(u32 word) {
-  return (float)(2u * (word >> 9) + 1u) * 5.9604644775390625e-08f;
-}
-
-ACCO_DEV float gumbel(u32 word) { return -logf(-logf(uniform01(word))); }
-
-struct Best {
-  float score;
-  int idx;
-};
-
-ACCO_DEV void better(Best& a, float score, int idx) {
-  if (score > a.score || (score == a.score && idx < a.idx)) {
-    a.score = score;
-    a.idx = idx;
-  }
-}
 
 // Block reductions. Every thread returns with the result; each ends on a
 // barrier, so its LDS may be rewritten at once.
@@ -195,12 +112,6 @@ ACCO_DEV void block_best(Best& best, float* sh_score, int* sh_idx) {
   __syncthreads();
   for (int w = 0; w < NWAVE; ++w) better(best, sh_score[w], sh_idx[w]);
   __syncthreads();
-}
-
-// The row's mass factor exp((x - max) / T); the same pure function of the
-// element in every pass. c2 = log2(e) / T, the argument is <= 0.
-ACCO_DEV float mass(u32 key, float vmax, float c2) {
-  return __builtin_amdgcn_exp2f((key_value(key) - vmax) * c2);
 }
 
 __global__ __launch_bounds__(BLOCK) void spec_rows_kernel(
@@ -273,12 +184,12 @@ __global__ __launch_bounds__(BLOCK) void spec_rows_kernel(
   u64 zp = 0ull, zq = 0ull;
   for_each_elem(prow, V, [&](u32 bits, int) {
     const u32 key = load_key(bits);
-    if (key != 0u) zp += (u64)(mass(key, vp, c2) * mscale);
+    if (key != 0u) zp += fixed_mass(key, vp, c2, mscale);
   });
   if (kq != 0u)
     for_each_elem(qrow, V, [&](u32 bits, int) {
       const u32 key = load_key(bits);
-      if (key != 0u) zq += (u64)(mass(key, vq, c2) * mscale);
+      if (key != 0u) zq += fixed_mass(key, vq, c2, mscale);
     });
   block_sum2(zp, zq, sh_sum);
   // the maximum's own mass is mscale exactly: both sums are >= mscale
@@ -374,20 +285,12 @@ extern "C" void acco_spec_verify(const void* p_logits, long long p_bs,
                                  long long eos_id, int* n_accept,
                                  long long* next_token, float* accept_prob,
                                  int* workspace, hipStream_t s) {
-  const bool greedy = temperature == 0.0f;
-  const float T = greedy ? 1.0f : temperature;
-  // log2(e) / T rounded once: the exponent of a mass is one product away
-  const float c2 = (float)(1.4426950408889634 / (double)T);
-  // V masses of at most 2^shift each sum below 2^62
-  int bits = 0;
-  while ((1ll << bits) < (long long)V) ++bits;
-  const int shift = 62 - bits < 40 ? 62 - bits : 40;
-  const float mscale = ldexpf(1.0f, shift);
+  const SamplingParams sp = sampling_params(temperature, V);
   hipLaunchKernelGGL(spec_rows_kernel, dim3(B * (k + 1)), dim3(BLOCK), 0, s,
                      (const u16*)p_logits, p_bs, p_ts, (const u16*)q_logits,
-                     q_bs, q_ts, draft_tokens, k, V, T, c2, mscale, greedy,
-                     seed, step, (const unsigned char*)done, accept_prob,
-                     workspace);
+                     q_bs, q_ts, draft_tokens, k, V, sp.T, sp.c2, sp.mscale,
+                     sp.greedy, seed, step, (const unsigned char*)done,
+                     accept_prob, workspace);
   hipLaunchKernelGGL(spec_select_kernel, dim3((B + 255) / 256), dim3(256), 0,
                      s, (const int*)workspace, B, k, done, eos_id, n_accept,
                      next_token);

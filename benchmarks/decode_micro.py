@@ -188,6 +188,26 @@ def bench_extend_kernel(B, T, L0, H=32, Hkv=8, D=64, calls=200,
         **{"us_" + k: v for k, v in out.items()}}), flush=True)
 
 
+def bench_sample_kernel(V=128256, B=8, calls=200, windows=3):
+    """ops.sample_logits alone (logits randn * 3, T = 0.8): us per call by
+    filter, best of `windows` windows of `calls` calls."""
+    x = (torch.randn(B, V, device="cuda") * 3).bfloat16()
+    row = {"bench": "sample_logits", "V": V, "B": B}
+    for name, kw in (("none", {}), ("top_k50_top_p0.9",
+                                    dict(top_k=50, top_p=0.9)),
+                     ("greedy", dict(temperature=0.0))):
+        def loop(count):
+            for i in range(count):
+                ops.sample_logits(x, **{"temperature": 0.8, "seed": 1,
+                                        "step": i, **kw})
+        loop(10)                                     # warm-up
+        torch.cuda.synchronize()
+        times = [event_seconds(lambda: loop(calls))[0] / calls * 1e6
+                 for _ in range(windows)]
+        row["us_" + name], row["us_" + name + "_windows"] = min(times), times
+    print(json.dumps(row), flush=True)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama-1b")
@@ -212,6 +232,7 @@ def main(argv=None):
         for B, T, L0 in ((1, 8, 1024), (8, 8, 4096), (1, 256, 3840)):
             for fp8 in (False, True):
                 bench_extend_kernel(B, T, L0, fp8=fp8)
+        bench_sample_kernel()
 
 
 if __name__ == "__main__":

@@ -287,6 +287,15 @@ def test_attn_decode_other_grids():
     assert torch.equal(_bits(a), _bits(b))
 
 
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("rep", range(1, 9))
+def test_attn_decode_every_group_size(D, rep):
+    """Every instantiation of the decode skeleton on the "odd" shape: splits
+    [0, 192) and [192, 300), one key beyond the boundary, a short last
+    split."""
+    check_decode("odd", (193, 300), 1, rep, D, 300)
+
+
 def test_attn_decode_strided_q():
     """q as the q section of a packed projection output (row stride W)."""
     q, kc, vc, cl = make_decode("strided", (100, 256), 2, 2, 64, 256)

@@ -146,6 +146,13 @@ def test_attn_decode_fp8_other_grids():
 
 
 @pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("rep", range(1, 9))
+def test_attn_decode_fp8_every_group_size(D, rep):
+    """The twin of TD.test_attn_decode_every_group_size."""
+    check("decode", "odd", (193, 300), 1, rep, D, 300, Hkv=1)
+
+
+@pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("c", TE.CASES, ids=lambda c: "-".join(
     "%s%d" % kv for kv in c.items()))
 def test_attn_extend_fp8_sweep(D, c):
