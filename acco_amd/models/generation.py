@@ -24,8 +24,9 @@ def generate(model, input_ids: torch.Tensor,
              prefill_chunk: int = 0,
              kv_dtype: Optional[torch.dtype] = None,
              weight_dtype: Optional[torch.dtype] = None,
-             draft=None, spec_k: int = 4
-             ) -> Tuple[torch.Tensor, torch.Tensor]:
+             draft=None, spec_k: int = 4,
+             act_dtype: Optional[torch.dtype] = None
+             ) ->Tuple[torch.Tensor, torch.Tensor]:
     """(tokens int64 [B, S + max_new], n_generated int64 [B]) for prompts
     `input_ids` [B, S] of `model` (LlamaForCausalLM or GPTNeoForCausalLM, in
     eval mode). Sequence b holds lens[b] <= S prompt tokens (None = all S),
@@ -57,6 +58,13 @@ def generate(model, input_ids: torch.Tensor,
     speculative round of a large batch) run ops.gemm_w8 / ops.gemm_w4, HIP
     kernels that read the codes as codes, up to ops.W8_GEMM_MAX_ROWS /
     ops.W4_GEMM_MAX_ROWS rows.
+    act_dtype: passed to quantize_weights when this call quantises the model
+    itself (weight_dtype torch.float4_e2m1fn_x2 only; None = off; a model
+    that is already quantised keeps its own setting). With
+    torch.float8_e4m3fn the prompt-width calls (65 rows and more: the
+    prefill, prefill_chunk slices) see activations rounded to OCP MXFP8 and
+    run ops.gemm_w4a8 on the block-scaled MFMA; decode-width calls do not:
+    they stay weight-only.
     draft: a model of the same interface and vocab_size (for one,
     quantize_weights(model, torch.float4_e2m1fn_x2) of `model` itself) turns
     on speculative decoding, spec_k >= 1 drafted tokens per round
@@ -76,7 +84,10 @@ def generate(model, input_ids: torch.Tensor,
             raise ValueError("weight_dtype must be None, torch.float8_e4m3fn "
                              f"or torch.float4_e2m1fn_x2, got {weight_dtype}")
         if not has_quantized_linears(model):
-            model = quantize_weights(model, weight_dtype)
+            model = quantize_weights(model, weight_dtype, act_dtype)
+    elif act_dtype is not None:
+        raise ValueError("act_dtype needs weight_dtype="
+                         "torch.float4_e2m1fn_x2")
     B, S = input_ids.shape
     max_new = int(max_new)
     if max_new < 0:

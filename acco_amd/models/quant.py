@@ -9,7 +9,11 @@ here trains.
 
 The same in OCP MXFP4 (`W4Linear`, `ops.linear_w4` / `ops.gemm_w4`): e2m1
 codes with one power-of-two scale per 32 weights
-(torch_ref.weight_quantize_mxfp4), about 0.53 bytes per weight."""
+(torch_ref.weight_quantize_mxfp4), about 0.53 bytes per weight. With
+`act_dtype=torch.float8_e4m3fn` a W4Linear also rounds the activations of its
+wide calls (65 rows and more) to OCP MXFP8 and multiplies both code sets on
+the block-scaled MFMA (`ops.gemm_w4a8`); decode-width calls stay
+weight-only."""
 
 from __future__ import annotations
 
@@ -21,6 +25,12 @@ import torch.nn as nn
 
 from acco_amd import ops
 from acco_amd.models.fuse import _FUSE_ATTRS
+
+
+def _check_act_dtype(act_dtype) -> None:
+    if act_dtype not in (None, torch.float8_e4m3fn):
+        raise ValueError("act_dtype must be None or torch.float8_e4m3fn, got "
+                         f"{act_dtype}")
 
 
 class _QuantLinear(nn.Module):
@@ -86,21 +96,35 @@ class W4Linear(_QuantLinear):
     """A linear whose weight is MXFP4: uint8 `codes` [out, in / 2] and uint8
     `scales` [out, in / 32] (buffers, as is the optional `bias`): forward is
     ops.linear_w4 up to 64 rows of x and ops.gemm_w4 beyond. in_features must
-    be a multiple of 32."""
+    be a multiple of 32.
+    act_dtype: None, or torch.float8_e4m3fn: calls of at least
+    max(65, ops.W4A8_GEMM_MIN_ROWS) rows (65 when that is None) go to
+    ops.gemm_w4a8, which rounds x to MXFP8; fewer rows are routed as without
+    it."""
 
     _SCALE, _DTYPES = "scales", (torch.uint8, torch.uint8)
     _OPS = ("linear_w4", "gemm_w4", "W4_GEMM_MAX_ROWS")
     _quantize = staticmethod(ops.torch_ref.weight_quantize_mxfp4)
 
-    def __init__(self, codes, scales, bias=None):
+    def __init__(self, codes, scales, bias=None, act_dtype=None):
         super().__init__(codes, scales, bias)
         self.out_features, self.in_features = codes.shape[0], 2 * codes.shape[1]
+        _check_act_dtype(act_dtype)
+        self.act_dtype = act_dtype
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.act_dtype is not None:
+            rows = x.numel() // max(x.shape[-1], 1)
+            if rows >= max(65, ops.W4A8_GEMM_MIN_ROWS or 65):
+                return ops.gemm_w4a8(x, self.codes, self.scales, self.bias)
+        return super().forward(x)
 
 
 FP4 = torch.float4_e2m1fn_x2
 
 
-def _copy_module(mod: nn.Module, dtype: torch.dtype) -> nn.Module:
+def _copy_module(mod: nn.Module, dtype: torch.dtype,
+                 act_dtype: Optional[torch.dtype] = None) -> nn.Module:
     """A new module tree over the same tensors: nn.Linear -> W8Linear (or
     W4Linear), every other module a shallow copy with its own parameter /
     buffer / child tables, so embeddings and norm weights are shared with the
@@ -109,11 +133,16 @@ def _copy_module(mod: nn.Module, dtype: torch.dtype) -> nn.Module:
         if dtype != FP4:
             return W8Linear.from_linear(mod)
         # MXFP4 blocks are 32 wide: a linear they do not tile stays as it is
-        return W4Linear.from_linear(mod) if mod.in_features % 32 == 0 else mod
+        if mod.in_features % 32 != 0:
+            return mod
+        new = W4Linear.from_linear(mod)
+        new.act_dtype = act_dtype
+        return new
     new = copy.copy(mod)
     new._parameters = dict(mod._parameters)
     new._buffers = dict(mod._buffers)
-    new._modules = {name: None if child is None else _copy_module(child, dtype)
+    new._modules = {name: None if child is None
+                    else _copy_module(child, dtype, act_dtype)
                     for name, child in mod._modules.items()}
     for attr in _FUSE_ATTRS:
         # arena views of the bf16 weights: the copy takes the per-projection
@@ -125,7 +154,8 @@ def _copy_module(mod: nn.Module, dtype: torch.dtype) -> nn.Module:
 
 @torch.no_grad()
 def quantize_weights(model: nn.Module,
-                     dtype: torch.dtype = torch.float8_e4m3fn) -> nn.Module:
+                     dtype: torch.dtype = torch.float8_e4m3fn,
+                     act_dtype: Optional[torch.dtype] = None) -> nn.Module:
     """A copy of `model` (LlamaForCausalLM or GPTNeoForCausalLM, in eval mode)
     for generation whose every nn.Linear is a W8Linear of the same weight; a
     tied lm_head gets codes of its own and the embedding stays as it is.
@@ -134,14 +164,22 @@ def quantize_weights(model: nn.Module,
     the original is not modified.
     dtype: torch.float8_e4m3fn (W8Linear) or torch.float4_e2m1fn_x2: MXFP4
     W4Linears, except that a linear whose in_features is not a multiple of 32
-    stays the original's bf16 nn.Linear in the copy."""
+    stays the original's bf16 nn.Linear in the copy.
+    act_dtype: None, or torch.float8_e4m3fn with the MXFP4 dtype only: every
+    W4Linear then sends its calls of 65 rows and more (the prefill, long
+    extends) to ops.gemm_w4a8, which rounds the activations to MXFP8;
+    decode-width calls stay weight-only. Anything else raises ValueError."""
+    _check_act_dtype(act_dtype)
+    if act_dtype is not None and dtype != FP4:
+        raise ValueError("quantize_weights: act_dtype needs dtype="
+                         f"torch.float4_e2m1fn_x2, got {dtype}")
     if model.training:
         raise ValueError("quantize_weights is for generation: call "
                          "model.eval() first")
     if dtype not in (torch.float8_e4m3fn, FP4):
         raise ValueError("quantize_weights: dtype must be torch.float8_e4m3fn "
                          f"or torch.float4_e2m1fn_x2, got {dtype}")
-    return _copy_module(model, dtype).eval()
+    return _copy_module(model, dtype, act_dtype).eval()
 
 
 def has_quantized_linears(model: nn.Module) -> bool:

@@ -541,6 +541,70 @@ def gemm_w4_tiles(m: int, n: int, k: int) -> Tuple[int, int, int, int]:
                                                         int(k)))
 
 
+# The fewest rows a W4Linear with act_dtype sends to gemm_w4a8 (never fewer
+# than 65: decode stays weight-only). Set by benchmarks/gemm_w4a8_micro.py,
+# the rule of W8_GEMM_MAX_ROWS mirrored: the smallest measured M from which
+# gemm_w4a8 with its quantiser is no slower than gemm_w4 at every shape and
+# every larger measured M; None: there is no such M, and an explicit
+# act_dtype still routes at 65. RESULTS.md, "MXFP4 x MXFP8 GEMM": at
+# 768 x 768 the quantiser's launch keeps gemm_w4a8 behind at every M measured.
+W4A8_GEMM_MIN_ROWS: Optional[int] = None
+
+
+def _as_kernel_rows(x: torch.Tensor) -> torch.Tensor:
+    """x [..., K] as the [M, K] the kernels take: re-strided as _gemm_wq
+    does."""
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    return x2
+
+
+def act_quantize_mxfp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(codes float8_e4m3fn [..., K], scales uint8 [..., K / 32]) of x in OCP
+    MXFP8, one e8m0 scale per 32 k of a row (torch_ref.act_quantize_mxfp8 has
+    the rule). On the GPU a bf16 x with K % 32 == 0 runs the HIP kernel
+    (act_quant.hip), bit for bit the reference; x may be a strided view with
+    a contiguous last dim. CPU tensors, other dtypes, K == 0 and
+    ACCO_FORCE_REF=1 run the torch reference."""
+    K = x.shape[-1]
+    if (_use_ref(x) or x.dtype != torch.bfloat16 or K % 32 != 0
+            or x.numel() == 0):
+        return torch_ref.act_quantize_mxfp8(x)
+    codes, scales = hip_ext().act_quantize_mxfp8(_as_kernel_rows(x))
+    return codes.view(x.shape), scales.view(*x.shape[:-1], K // 32)
+
+
+def gemm_w4a8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The W4A8 product: y [..., N] = dequant(act_quantize_mxfp8(x)) @
+    dequant(codes, scales)^T (+ bias) for an MXFP4 weight
+    (torch_ref.linear_w4a8 has the semantics), the leading dims of x
+    flattened to M. Unlike gemm_w4 it rounds x to e4m3.
+
+    On the GPU, bf16 x and K % 128 == 0 run two HIP kernels for every M >= 1:
+    act_quant.hip writes x as MXFP8 codes and scales, and gemm_w4a8.hip
+    multiplies both code sets as they are on the block-scaled MFMA, fp32
+    accumulation, one rounding to bf16. x may be a strided view with a
+    contiguous last dim. CPU tensors, other dtypes, other K and
+    ACCO_FORCE_REF=1 run torch_ref.linear_w4a8."""
+    K, N = x.shape[-1], codes.shape[0]
+    if (_use_ref(x) or x.dtype != torch.bfloat16
+            or codes.dtype != torch.uint8 or K % 128 != 0 or K == 0):
+        return torch_ref.linear_w4a8(x, codes, scales, bias)
+    if x.numel() == 0:
+        return x.new_empty(*x.shape[:-1], N)
+    ext = hip_ext()
+    xq, xs = ext.act_quantize_mxfp8(_as_kernel_rows(x))
+    return ext.gemm_w4a8(xq, xs, codes, scales, bias).view(*x.shape[:-1], N)
+
+
+def gemm_w4a8_tiles(m: int, n: int, k: int) -> Tuple[int, int, int, int]:
+    """gemm_w8_tiles for the HIP gemm_w4a8."""
+    return tuple(int(v) for v in hip_ext().gemm_w4a8_grid(int(m), int(n),
+                                                          int(k)))
+
+
 def sample_logits(logits: torch.Tensor, *, temperature: float, top_k: int = 0,
                   top_p: float = 1.0, seed: int, step: int,
                   done: Optional[torch.Tensor] = None, eos_id: int = -1

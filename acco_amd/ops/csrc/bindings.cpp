@@ -1562,6 +1562,86 @@ at::Tensor gemm_w4(at::Tensor x, at::Tensor codes, at::Tensor scales,
   });
 }
 
+// ---- W4A8 (act_quant.hip, gemm_w4a8.hip): MXFP8 activations against the
+// MXFP4 weight on the block-scaled MFMA
+// (codes float8_e4m3fn [M, K], scales uint8 [M, K / 32]) of x. The argument
+// contract: x CUDA bf16 [M, K], M >= 1, K a positive multiple of 32, a
+// contiguous last dim, rows stride(0) >= K apart (a multiple of 8) on a
+// 16-byte aligned base.
+std::vector<at::Tensor> act_quantize_mxfp8(at::Tensor x) {
+  check_skinny_x(x);
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1 && K >= 32 && K % 32 == 0 && K < (1LL << 24) &&
+              M * K < (1LL << 40),
+              "act_quantize_mxfp8: need M >= 1, K < 2^24 a positive multiple "
+              "of 32 and M * K < 2^40, got M=", M, " K=", K);
+  const int64_t rs = M > 1 ? x.stride(0) : K;
+  TORCH_CHECK(x.stride(1) == 1 && rs >= K && rs % 8 == 0 && aligned_to(x, 16),
+              "x must be 16-byte aligned with a contiguous last dim and rows "
+              "a multiple of 8 elements, at least K, apart, got strides ",
+              x.strides());
+  auto codes = at::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto scales = at::empty({M, K / 32}, x.options().dtype(at::kByte));
+  acco_act_quant_mxfp8(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), M,
+                       (int)K, rs, cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {codes, scales};
+}
+
+std::vector<int64_t> gemm_w4a8_grid(int64_t M, int64_t N, int64_t K) {
+  return gemm_wq_grid("gemm_w4a8", acco_gemm_w4a8_grid, 128, M, N, K);
+}
+
+// y [M, N] bf16 = dequant(xq, xs) . dequant(codes, scales)^T (+ bias). The
+// argument contract: xq contiguous float8_e4m3fn [M, K] and xs contiguous
+// uint8 [M, K / 32] as act_quantize_mxfp8 returns them, 16- and 4-byte
+// aligned; codes, scales and bias as gemm_w4's; all on xq's device;
+// gemm_wq_grid has the sizes.
+at::Tensor gemm_w4a8(at::Tensor xq, at::Tensor xs, at::Tensor codes,
+                     at::Tensor scales, c10::optional<at::Tensor> bias) {
+  TORCH_CHECK(xq.is_cuda() && xq.scalar_type() == at::kFloat8_e4m3fn &&
+              xq.dim() == 2 && xq.is_contiguous(),
+              "xq must be contiguous CUDA float8_e4m3fn [M, K], got ",
+              xq.scalar_type(), " ", xq.sizes(), " on ", xq.device());
+  const int64_t M = xq.size(0), K = xq.size(1);
+  TORCH_CHECK(codes.is_cuda() && codes.device() == xq.device() &&
+              codes.scalar_type() == at::kByte && codes.is_contiguous() &&
+              codes.dim() == 2 && codes.size(1) * 2 == K,
+              "codes must be contiguous uint8 [N, K / 2 = ", K / 2, "] on ",
+              xq.device(), ", got ", codes.scalar_type(), " ", codes.sizes(),
+              " on ", codes.device());
+  const int64_t N = codes.size(0);
+  const int64_t n_split = gemm_w4a8_grid(M, N, K)[2];
+  const std::pair<const at::Tensor*, int64_t> sc[] = {{&xs, M}, {&scales, N}};
+  for (const auto& [t, rows] : sc)
+    TORCH_CHECK(t->is_cuda() && t->device() == xq.device() &&
+                t->scalar_type() == at::kByte && t->is_contiguous() &&
+                t->dim() == 2 && t->size(0) == rows && t->size(1) * 32 == K,
+                "xs / scales must be contiguous uint8 [M or N, K / 32] = [",
+                rows, ", ", K / 32, "] on ", xq.device(), ", got ",
+                t->scalar_type(), " ", t->sizes(), " on ", t->device());
+  TORCH_CHECK(aligned_to(xq, 16) && aligned_to(codes, 16) &&
+              aligned_to(xs, 4),
+              "xq and codes must be 16-byte aligned, xs 4-byte aligned");
+  if (bias.has_value())
+    TORCH_CHECK(bias->is_cuda() && bias->device() == xq.device() &&
+                bias->scalar_type() == at::kBFloat16 &&
+                bias->is_contiguous() && bias->dim() == 1 &&
+                bias->size(0) == N, "bias must be contiguous bf16 [N] = [", N,
+                "] on ", xq.device(), ", got ", bias->scalar_type(), " ",
+                bias->sizes(), " on ", bias->device());
+  auto y = at::empty({M, N}, xq.options().dtype(at::kBFloat16));
+  auto ws = at::empty({n_split > 1 ? n_split * M * N : 0},
+                      xq.options().dtype(at::kFloat));
+  acco_gemm_w4a8(xq.data_ptr(), xs.data_ptr(), codes.data_ptr(),
+                 scales.data_ptr(), bias.has_value() ? bias->data_ptr()
+                                                     : nullptr,
+                 y.data_ptr(), ws.data_ptr<float>(), (int)M, (int)N, (int)K,
+                 cur_stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return y;
+}
+
 // ---- on-device sampling (sample.hip)
 // (token int64 [B], logprob fp32 [B], thr bf16 [B], n_kept int32 [B]) of one
 // draw per row. The argument contract: logits CUDA bf16 [B, V] whose last dim
@@ -1763,6 +1843,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("K"));
   m.def("gemm_w4", &gemm_w4, py::arg("x"), py::arg("codes"),
         py::arg("scales"), py::arg("bias"));
+  m.def("act_quantize_mxfp8", &act_quantize_mxfp8, py::arg("x"));
+  m.def("gemm_w4a8_grid", &gemm_w4a8_grid, py::arg("M"), py::arg("N"),
+        py::arg("K"));
+  m.def("gemm_w4a8", &gemm_w4a8, py::arg("xq"), py::arg("xs"),
+        py::arg("codes"), py::arg("scales"), py::arg("bias"));
   m.def("fused_adamw", &fused_adamw,
         "Fused sharded AdamW (gfx950): cast+scale+AdamW+bf16 writeout; "
         "commit=false = ACCO tentative step");

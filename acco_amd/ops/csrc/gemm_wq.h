@@ -118,6 +118,14 @@ ACCO_DEV void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// workgroup `flat` of nwg runs on XCD flat % 8: give each XCD a contiguous
+// range of the numbering (row block fastest, then weight block, then split)
+ACCO_DEV int xcd_remap(int flat, int nwg) {
+  const int q = nwg / 8, r = nwg % 8;
+  const int xcd = flat % 8, idx = flat / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // A format F gives: Scale, Finish, kStep (k per 16-byte load of a tile, KT a
 // multiple of it), Frag (a step's codes of the lane's four tiles), Ptr and
 // ptrs (where the lane's loads start), load(frag, ptr, k) and
@@ -137,15 +145,8 @@ void gemm_kernel(const u16* __restrict__ x, const u8* __restrict__ codes,
   const int lane = tid % kWave, wave = tid / kWave;
   const int j = lane % 16, g = lane / 16;
 
-  // workgroup `flat` runs on XCD flat % 8: give each XCD a contiguous range
-  // of the numbering (row block fastest, then weight block, then split)
-  int flat = __builtin_amdgcn_workgroup_id_x();
-  {
-    const int nwg = m_blocks * n_blocks * n_split;
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = flat % 8, idx = flat / 8;
-    flat = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int flat = xcd_remap(__builtin_amdgcn_workgroup_id_x(),
+                             m_blocks * n_blocks * n_split);
   const int bm = flat % m_blocks, bn = flat / m_blocks % n_blocks;
   const int split = flat / m_blocks / n_blocks;
   const int m0 = bm * BM, m_live = min(BM, M - m0);

@@ -187,6 +187,32 @@ void acco_gemm_w4(const void* x, const void* codes, const void* scales,
                   const void* bias, void* y, float* workspace, int M, int N,
                   int K, long long x_rs, hipStream_t stream);
 
+// ---- act_quant.hip
+// OCP MXFP8 of activation rows: x [M, K] bf16 (rows x_rs elements apart, a
+// multiple of 8, on a 16-byte aligned base) -> codes [M, K] e4m3 and scales
+// [M, K / 32] e8m0 bytes, both contiguous, bit for bit
+// torch_ref.act_quantize_mxfp8. M >= 1, K % 32 == 0, M * K < 2^40.
+void acco_act_quant_mxfp8(const void* x, void* codes, void* scales,
+                          long long M, int K, long long x_rs,
+                          hipStream_t stream);
+
+// ---- gemm_w4a8.hip
+// y [M, N] bf16 contiguous = dequant(xq [M, K] e4m3, xs [M, K / 32] e8m0)
+// . dequant(codes [N, K / 2], scales [N, K / 32])^T (+ bias [N] bf16,
+// nullable) on the block-scaled MFMA; xq, xs as acco_act_quant_mxfp8 stores
+// them, the weight as acco_gemm_w4's. M >= 1, N >= 1, K % 128 == 0, K < 2^24,
+// M * N and the workgroup count below 2^31. m_blocks blocks of 64 rows of x
+// by n_blocks blocks of 256 weight rows, each over n_split workgroups of
+// k_chunk columns (host only, a function of the three sizes); workspace:
+// n_split * M * N fp32 when n_split > 1 (written before it is read), unused
+// otherwise.
+void acco_gemm_w4a8_grid(int M, int N, int K, int* m_blocks, int* n_blocks,
+                         int* n_split, int* k_chunk);
+void acco_gemm_w4a8(const void* xq, const void* xs, const void* codes,
+                    const void* scales, const void* bias, void* y,
+                    float* workspace, int M, int N, int K,
+                    hipStream_t stream);
+
 // ---- ce.hip
 // bf16 logits on a 16-byte aligned base (any V). A token is valid iff
 // 0 <= target < V; any other target (-100, >= V) is ignored: lse 0, no loss,

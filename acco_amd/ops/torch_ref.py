@@ -274,6 +274,59 @@ def linear_w4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
     return y.to(x.dtype)
 
 
+def act_quantize_mxfp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(codes float8_e4m3fn [..., K], scales uint8 [..., K / 32]) of
+    activation rows x [..., K] in OCP MXFP8; K must be a multiple of 32. Every
+    32 consecutive k share one e8m0 scale byte s, the scale 2^(s - 127).
+
+    The exponent is weight_quantize_mxfp4's rule with e4m3's largest exponent
+    in place of e2m1's, in exact operations: with amax the block's largest
+    |x| in fp32, e = floor(log2(amax)) - 8 (torch.frexp), clamped into
+    [-120, 120]; s = e + 127. A zero block takes byte 127 and zero codes; byte
+    255 (NaN) is never produced. A code is x / 2^e (exact) rounded to the
+    nearest e4m3, ties to even, subnormals kept, saturating at +-448 (the
+    clamp is applied in the wide type: torch's e4m3 cast does not saturate):
+    amax / 2^e lies in [256, 512), so values in (448, 512) * 2^e clip to
+    448 * 2^e. That is the specification's behaviour, not an oversight.
+    Non-finite x is outside the contract."""
+    K = x.shape[-1]
+    if K % 32 != 0:
+        raise ValueError(f"act_quantize_mxfp8 needs K % 32 == 0, got {K}")
+    blocks = x.detach().float().reshape(*x.shape[:-1], K // 32, 32)
+    amax = blocks.abs().amax(dim=-1)
+    e = torch.frexp(amax)[1] - 9      # amax = m * 2^exp, m in [0.5, 1)
+    e = torch.where(amax > 0, e.clamp(-120, 120), torch.zeros_like(e))
+    v = torch.ldexp(blocks.double(), -e[..., None])          # exact
+    codes = v.clamp(-E4M3_MAX, E4M3_MAX).float().to(torch.float8_e4m3fn)
+    return codes.reshape(x.shape), (e + 127).to(torch.uint8)
+
+
+def act_dequantize_mxfp8(codes: torch.Tensor, scales: torch.Tensor,
+                         dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The [..., K] values of MXFP8 codes [..., K] and scales [..., K / 32] in
+    `dtype`: exact in fp32 and wider (a four-bit significand times a power of
+    two), and in bf16 where the value is a normal bf16."""
+    K = codes.shape[-1]
+    scale = torch.ldexp(torch.ones((), device=codes.device),
+                        scales.int() - 127).to(dtype)
+    blocks = codes.to(dtype).reshape(*codes.shape[:-1], K // 32, 32)
+    return (blocks * scale[..., None]).reshape(codes.shape)
+
+
+def linear_w4a8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [..., N] = dequant(act_quantize_mxfp8(x)) @ dequant(codes, scales)^T
+    (+ bias [N]) for weights stored by weight_quantize_mxfp4: linear_w4 with
+    x rounded to MXFP8 first. Computed in fp32 (fp64 for an fp64 x) and
+    returned in x's dtype. Non-finite x is outside the contract."""
+    acc = torch.promote_types(x.dtype, torch.float32)
+    xq = act_dequantize_mxfp8(*act_quantize_mxfp8(x), acc)
+    y = xq @ weight_dequantize_mxfp4(codes, scales, acc).t()
+    if bias is not None:
+        y = y + bias.to(acc)
+    return y.to(x.dtype)
+
+
 @torch.no_grad()
 def kv_append(k_cache: torch.Tensor, v_cache: torch.Tensor,
               cache_len: torch.Tensor, k: torch.Tensor, v: torch.Tensor,

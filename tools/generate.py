@@ -17,7 +17,8 @@ models.quantize_weights(model): every linear as e4m3 codes with one scale per
 output row, half the weight bytes per token (any of the paths above; the HIP
 kernel serves a bf16 model on the GPU). --weight-dtype fp4 does the same in
 OCP MXFP4: e2m1 codes with one power-of-two scale per 32 weights, about 0.53
-bytes per weight. --draft-weight-dtype {fp8,fp4} --spec-k K (implies
+bytes per weight; with it, --act-dtype fp8 rounds the activations of the
+prefill to OCP MXFP8 for the MXFP4 x MXFP8 GEMM. --draft-weight-dtype {fp8,fp4} --spec-k K (implies
 --device-sampling; not with --top-k / --top-p) decodes speculatively with a
 quantised copy of the checkpoint as its own draft: K drafted tokens per
 round, checked by one forward of the model and ops.spec_verify. Beyond the
@@ -124,6 +125,11 @@ def main(argv=None) -> str:
                          "linears hold e4m3 weight codes with one scale per "
                          "output row; fp4: MXFP4 codes with one scale per 32 "
                          "weights; bf16: the checkpoint's own weights")
+    ap.add_argument("--act-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8 (needs --weight-dtype fp4): calls of 65 rows "
+                         "and more (the prefill) round their activations to "
+                         "OCP MXFP8 and run the MXFP4 x MXFP8 GEMM; decode "
+                         "steps stay weight-only")
     ap.add_argument("--device-sampling", action="store_true",
                     help="sample on the model's device with "
                          "acco_amd.models.generate (implies --kv-cache): no "
@@ -148,6 +154,8 @@ def main(argv=None) -> str:
         ap.error("need --prefill-chunk >= 0")
     if args.top_k < 0 or not args.top_p > 0:
         ap.error("need --top-k >= 0 and --top-p > 0")
+    if args.act_dtype == "fp8" and args.weight_dtype != "fp4":
+        ap.error("--act-dtype fp8 needs --weight-dtype fp4")
     if args.draft_weight_dtype is not None:
         if args.top_k != 0 or args.top_p < 1.0:
             ap.error("--draft-weight-dtype does not combine with --top-k / "
@@ -177,7 +185,9 @@ def main(argv=None) -> str:
         draft = quantize_weights(model.eval(), codes[args.draft_weight_dtype])
     if args.weight_dtype != "bf16":
         from acco_amd.models import quantize_weights
-        model = quantize_weights(model.eval(), codes[args.weight_dtype])
+        model = quantize_weights(
+            model.eval(), codes[args.weight_dtype],
+            torch.float8_e4m3fn if args.act_dtype == "fp8" else None)
 
     ids = torch.tensor([tok.encode(args.prompt).ids], device=device)
     kv_dtype = torch.float8_e4m3fn if args.kv_dtype == "fp8" else None
